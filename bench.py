@@ -46,6 +46,15 @@ H2D + one pitched D2H of a step issued together — what a PCIe-bound step
 converges to (e.g. 0.309 ms per pair vs a 0.318 ms step at N=1).
 
 Data: synthetic random bytes (no image ships with the reference).
+
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only what the
+headline needs: set-up, warm-up, the K timed steps, the JSON line.  Everything
+else described above (the CPU-oracle check and "mismatches", the replayed
+"windows", "latency_ms", "copy_floor", "loop_only", "halo_modes" and the halo
+selection, the resident loops) runs only with --full, after the timed steps.
+--dump-outputs DIR writes the rows the last timed step returned as
+DIR/output.npy (float32; the synthetic input is a function of --seed alone, so
+two builds run with the same arguments can be compared output for output).
 """
 from __future__ import annotations
 
@@ -132,8 +141,8 @@ def parse():
                    help="with --emulate: also hold a 1-rank RCCL communicator during the timed region (its "
                         "streams and queues, as a real N>1 rank has)")
     p.add_argument("--exchange-check", choices=["auto", "on", "off"], default="auto",
-                   help="N>1: after the headline timing, also time the halo modes of --halo-modes (ghost rows "
-                        "moved GPU-to-GPU) with the same K steps, and compare their bytes with the headline "
+                   help="N>1 with --full: after the headline timing, also time the halo modes of --halo-modes (ghost "
+                        "rows moved GPU-to-GPU) with the same K steps, and compare their bytes with the headline "
                         "result; reported under 'halo_modes' (auto: on for N>1)")
     p.add_argument("--halo-modes", default=",".join(HALO_MODES),
                    help="comma list of the halo modes timed after the headline at N>1: " + ", ".join(HALO_MODES))
@@ -168,8 +177,8 @@ def parse():
                         "pipeline: --graph-capture off or --step-graphs off) and write them to --trace-out")
     p.add_argument("--trace-out", default="gpurun_out/pipeline_trace.json")
     p.add_argument("--check", dest="check", action="store_true", default=True,
-                   help="after timing (outside the timed region), compare every rank's newest image, and every halo "
-                        "mode's at N>1, with the CPU oracle; 'mismatches' in the JSON line (default on)")
+                   help="with --full: after timing (outside the timed region), compare every rank's newest image, and "
+                        "every halo mode's at N>1, with the CPU oracle; 'mismatches' in the JSON line (default on)")
     p.add_argument("--no-check", dest="check", action="store_false", help="skip the oracle check (sweeps)")
     p.add_argument("--pool-queues", dest="cu_mask_queues", action="store_false", default=True,
                    help="slot streams from the runtime's queue pool (default: each on its own CU-masked hardware "
@@ -182,8 +191,8 @@ def parse():
     p.add_argument("--numa-bind", choices=["on", "off"], default="on",
                    help="restrict each rank to its GPU's NUMA node (default on)")
     p.add_argument("--diag-windows", type=int, default=8, metavar="W",
-                   help="after the timed region, replay the identical K-image window W times unmarked and W times "
-                        "with per-image completion marks; reported under 'windows' (0 = off)")
+                   help="with --full: after the timed region, replay the identical K-image window W times unmarked and "
+                        "W times with per-image completion marks; reported under 'windows' (0 = off)")
     p.add_argument("--mark-timed", action="store_true",
                    help="diagnostics: completion marks in the TIMED window too (adds one event per image; the "
                         "line is flagged 'timed_window_marked')")
@@ -199,7 +208,20 @@ def parse():
     p.add_argument("--native", action="store_true",
                    help="run the same serving step on the native stack: the in-tree `conv --bench` (ROCm's HIP "
                         "runtime, no torch; its fork launcher for N > 1) and print its JSON line")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run everything beside the headline figure: the CPU-oracle check "
+                        "(--check), the replayed windows (--diag-windows), single-image latency, the copy floors, "
+                        "the device-resident loop and, at N>1 or with --emulate, the other halo modes and resident "
+                        "loops (--exchange-check, --resident-loop).  Without it (default) a run sets up, warms up, "
+                        "times --steps steps and prints the line; those options then have no effect")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps write the rows the last timed step returned (the pinned output buffer "
+                        "of its slot, this rank's owned rows) to DIR/output.npy (N>1: DIR/output_rank<R>.npy) as "
+                        "float32; outputs over the size limit are written as a fixed, seeded sample of their bytes")
+    a = p.parse_args()
+    if a.dump_outputs and a.native:
+        p.error("--dump-outputs needs the torch pipeline (not --native)")
+    return a
 
 
 def oracle_rows(a, band):
@@ -505,6 +527,29 @@ def timed_steps(blur, steps: int, reps: int, timeout_s: float):
     return max_over_ranks(mine), mine
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6  # --dump-outputs: all ranks' files together stay below this
+
+
+def dump_outputs(directory: str, rows, rank: int, world: int, seed: int) -> str:
+    """--dump-outputs: this rank's newest result (uint8 rows as the pipeline's
+    caller receives them) as float32 in DIR/output.npy (N>1: one file per
+    rank).  An output whose float32 copy would exceed this rank's share of
+    DUMP_LIMIT_BYTES is written as a sample instead: the bytes at sorted
+    positions drawn from default_rng(seed), the same positions in every run
+    with the same arguments."""
+    import numpy as np
+
+    rows = np.asarray(rows)
+    limit = DUMP_LIMIT_BYTES // 4 // max(1, world)
+    if rows.size > limit:
+        idx = np.sort(np.random.default_rng(int(seed)).integers(0, rows.size, size=limit))
+        rows = rows.reshape(-1)[idx]
+    os.makedirs(directory, exist_ok=True)
+    path = os.path.join(directory, "output.npy" if world == 1 else f"output_rank{rank}.npy")
+    np.save(path, rows.astype(np.float32))
+    return path
+
+
 def spawn_ranks(a) -> int:
     """`bench.py --gpus N` (N > 1) started without a launcher: start the N
     ranks through torch.distributed.run as CHILD processes (this process has
@@ -680,6 +725,91 @@ def window_diagnostics(blur, a, count: int) -> dict:
     return out
 
 
+def measure_extras(blur, a, ctx, device) -> dict:
+    """--full: the figures beside the headline, measured after it on the
+    headline's own pipeline (every rank must call it): single-image latency,
+    the copy floors and the device-resident loop; the JSON line's
+    latency_ms, copy_floor and loop_only."""
+    import torch
+
+    import pconv
+    from pconv.parallel.bootstrap import barrier, max_over_ranks
+
+    # ---- extra: single-image latency (one image in flight, nothing else
+    # queued): H2D + reps + D2H, the reference's GPU_convolution() scope.
+    lat = []
+    for _ in range(max(3, min(20, a.steps))):
+        t = time.perf_counter()
+        blur.step(a.reps)
+        lat.append(time.perf_counter() - t)
+    lat.sort()
+    latency_ms = max_over_ranks(lat[len(lat) // 2]) * 1e3
+    b = blur.band
+    h2d_ms, d2h_ms = copy_floor_ms(blur.inputs[0].size, b.rows * blur.row_bytes, device)
+    h2d_ms = max_over_ranks(h2d_ms / 1e3) * 1e3
+    d2h_ms = max_over_ranks(d2h_ms / 1e3) * 1e3
+    # ... and both directions at once, pitched like the pipeline's copies: the
+    # floor a PCIe-bound step converges to (diagnostic only: never fatal)
+    try:
+        probe = pconv.native.CopyProbe(device, blur.row_bytes, blur.inputs[0].size // blur.row_bytes, b.rows)
+    except Exception as e:  # noqa: BLE001
+        print(f"bench: copy pair floor not measured: {e}", file=sys.stderr)
+        probe = None
+
+    def pair_run(n):
+        try:
+            return probe.run(n) if probe is not None else -1.0
+        except Exception as e:  # noqa: BLE001
+            print(f"bench: copy pair floor not measured: {e}", file=sys.stderr)
+            return -1.0
+
+    # per rank: alone on the node (one rank at a time) and with every rank copying at once (N > 1: whether
+    # the ranks' host paths are independent, or share host DRAM / a switch)
+    pair_solo, pair_conc = copy_floors(pair_run, ctx.world, ctx.rank)
+    del probe  # its pinned rows and device frames
+    pair_ms = max(pair_conc)
+
+    # ---- extra: device-resident loop only (reps on the resident band)
+    eng = blur.engine
+    ls = a.loop_steps if a.loop_steps is not None else a.steps
+    def loop_once():
+        if blur.preload_halo:
+            eng.set_halo_valid(True)  # ghost rows stay resident (timing only)
+        eng.run(a.reps)
+
+    for _ in range(3):
+        loop_once()
+        eng.synchronize()
+    barrier()
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    for _ in range(ls):
+        loop_once()
+    eng.synchronize()
+    torch.cuda.synchronize()
+    barrier()
+    loop_elapsed = max_over_ranks(time.perf_counter() - t1)
+
+    px = a.width * a.height * a.reps
+    loop_value = px * ls / loop_elapsed / 1e6 if ls else None
+    return {
+        "latency_ms": round(latency_ms, 4),
+        "copy_floor": {"h2d_ms": round(h2d_ms, 4), "d2h_ms": round(d2h_ms, 4),
+                       "floor_ms": round(max(h2d_ms, d2h_ms), 4),
+                       # one pitched H2D + one pitched D2H of a step issued together (the PCIe-bound
+                       # pipeline's floor; null if the measurement failed)
+                       "pair_ms": round(pair_ms, 4) if pair_ms > 0 else None,
+                       # per rank: alone (one rank at a time), and all ranks at once between two barriers
+                       "pair_ms_solo": [round(x, 4) for x in pair_solo],
+                       "pair_ms_concurrent": [round(x, 4) for x in pair_conc]},
+        "loop_only": {
+            "ms_per_step": round(loop_elapsed / ls * 1e3, 4) if ls else None,
+            "mpix_per_s": round(loop_value, 2) if loop_value else None,  # (reps 0: copy-only diagnostics)
+            "us_per_rep": round(loop_elapsed / ls / a.reps * 1e6, 3) if ls and a.reps else None,
+        },
+    }
+
+
 def hw_queue_budget(a) -> int:
     """GPU_MAX_HW_QUEUES for this process.  With CU-masked slot streams (the
     default) every image slot has its own dedicated hardware queue outside
@@ -743,6 +873,10 @@ def main():
         a.slots = 4
     if a.native:
         sys.exit(run_native(a))
+    if not a.full:
+        # a plain run measures the headline figure only: nothing after the
+        # timed steps but the optional output dump and the JSON line
+        a.check, a.diag_windows, a.exchange_check, a.resident_loop = False, 0, "off", "off"
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ and not a.emulate:
         sys.exit(spawn_ranks(a))
     # The runtime's hardware-queue pool (must be set before the HIP runtime
@@ -822,8 +956,9 @@ def main():
     barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    last_slot = None
     for _ in range(a.steps):
-        blur.submit(a.reps)
+        last_slot = blur.submit(a.reps)
     blur.drain()
     torch.cuda.synchronize()
     barrier()
@@ -832,6 +967,9 @@ def main():
     per_rank = gather_floats(mine)  # diagnostics: load balance across ranks
     timed_marks = blur.pipe.marks() if a.mark_timed else None
     queues_at_timed = kfd_queue_count()
+    # ---- --dump-outputs: what the last timed step returned (its slot's output rows), before anything else runs
+    if a.dump_outputs and last_slot is not None:
+        dump_outputs(a.dump_outputs, blur.outputs[last_slot], ctx.rank, ctx.world, a.seed)
     # ---- diagnostics (not timed): the same window replayed, plain and marked
     windows = window_diagnostics(blur, a, a.diag_windows) if a.diag_windows > 0 else None
     # PCIe bytes per image of every rank (band + pre-loaded ghost rows in, owned rows out): whether an N>1
@@ -855,66 +993,13 @@ def main():
             with open(a.trace_out, "w") as f:
                 json.dump({"stages": ["slot", "h2d_start", "h2d_end", "reps_end", "d2h_end"], "ms": rows,
                            "args": vars(a)}, f)
-    # ---- extra: single-image latency (one image in flight, nothing else
-    # queued): H2D + reps + D2H, the reference's GPU_convolution() scope.
-    lat = []
-    for _ in range(max(3, min(20, a.steps))):
-        t = time.perf_counter()
-        blur.step(a.reps)
-        lat.append(time.perf_counter() - t)
-    lat.sort()
-    latency_ms = max_over_ranks(lat[len(lat) // 2]) * 1e3
-    b = blur.band
-    h2d_ms, d2h_ms = copy_floor_ms(blur.inputs[0].size, b.rows * blur.row_bytes, device)
-    h2d_ms = max_over_ranks(h2d_ms / 1e3) * 1e3
-    d2h_ms = max_over_ranks(d2h_ms / 1e3) * 1e3
-    # ... and both directions at once, pitched like the pipeline's copies: the
-    # floor a PCIe-bound step converges to (diagnostic only: never fatal)
-    try:
-        probe = pconv.native.CopyProbe(device, blur.row_bytes, blur.inputs[0].size // blur.row_bytes, b.rows)
-    except Exception as e:  # noqa: BLE001
-        print(f"bench: copy pair floor not measured: {e}", file=sys.stderr)
-        probe = None
-
-    def pair_run(n):
-        try:
-            return probe.run(n) if probe is not None else -1.0
-        except Exception as e:  # noqa: BLE001
-            print(f"bench: copy pair floor not measured: {e}", file=sys.stderr)
-            return -1.0
-
-    # per rank: alone on the node (one rank at a time) and with every rank copying at once (N > 1: whether
-    # the ranks' host paths are independent, or share host DRAM / a switch)
-    pair_solo, pair_conc = copy_floors(pair_run, ctx.world, ctx.rank)
-    del probe  # its pinned rows and device frames
-    pair_ms = max(pair_conc)
+    # ---- --full: single-image latency, copy floors, device-resident loop (not timed)
+    extras = measure_extras(blur, a, ctx, device) if a.full else {}
     if a.emulate:
         world = 1
 
-    # ---- extra: device-resident loop only (reps on the resident band)
-    eng = blur.engine
-    ls = a.loop_steps if a.loop_steps is not None else a.steps
-    def loop_once():
-        if blur.preload_halo:
-            eng.set_halo_valid(True)  # ghost rows stay resident (timing only)
-        eng.run(a.reps)
-
-    for _ in range(3):
-        loop_once()
-        eng.synchronize()
-    barrier()
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    for _ in range(ls):
-        loop_once()
-    eng.synchronize()
-    torch.cuda.synchronize()
-    barrier()
-    loop_elapsed = max_over_ranks(time.perf_counter() - t1)
-
     px = a.width * a.height * a.reps
     value = px * a.steps / elapsed / 1e6
-    loop_value = px * ls / loop_elapsed / 1e6 if ls else None
     runtime = pconv.native.runtime_info()  # the HIP runtime / RCCL this process actually runs on
     head_mode = "preload" if blur.preload_halo else ("none" if world == 1 else "event")
     out = None
@@ -965,20 +1050,7 @@ def main():
                 "qualify_staging": a.qualify_staging == "on",
                 "flush_staging": a.flush_staging == "on",
             },
-            "latency_ms": round(latency_ms, 4),
-            "copy_floor": {"h2d_ms": round(h2d_ms, 4), "d2h_ms": round(d2h_ms, 4),
-                           "floor_ms": round(max(h2d_ms, d2h_ms), 4),
-                           # one pitched H2D + one pitched D2H of a step issued together (the PCIe-bound
-                           # pipeline's floor; null if the measurement failed)
-                           "pair_ms": round(pair_ms, 4) if pair_ms > 0 else None,
-                           # per rank: alone (one rank at a time), and all ranks at once between two barriers
-                           "pair_ms_solo": [round(x, 4) for x in pair_solo],
-                           "pair_ms_concurrent": [round(x, 4) for x in pair_conc]},
-            "loop_only": {
-                "ms_per_step": round(loop_elapsed / ls * 1e3, 4) if ls else None,
-                "mpix_per_s": round(loop_value, 2) if loop_value else None,  # (reps 0: copy-only diagnostics)
-                "us_per_rep": round(loop_elapsed / ls / a.reps * 1e6, 3) if ls and a.reps else None,
-            },
+            **extras,  # --full: latency_ms, copy_floor, loop_only
             "device": torch.cuda.get_device_name(device),
             "runtime": runtime,
             "rccl": runtime["rccl_version"],

@@ -320,8 +320,8 @@ def test_bench_four_ranks_100_reps(height, mode):
     port = _port()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=4",
            "--master-addr", "127.0.0.1", f"--master-port={port}", os.path.join(ROOT, "bench.py"),
-           "--gpus", "4", "--steps", "3", "--warmup", "1", "--transport", "gloo-host", "--check", "--reps", "100",
-           "--width", "96", "--height", str(height), "--halo-mode", mode, "--exchange-check", "off"]
+           "--gpus", "4", "--steps", "3", "--warmup", "1", "--full", "--transport", "gloo-host", "--check",
+           "--reps", "100", "--width", "96", "--height", str(height), "--halo-mode", mode, "--exchange-check", "off"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -337,7 +337,7 @@ def test_bench_four_ranks_100_reps(height, mode):
 
 def test_bench_spawns_its_ranks():
     """`bench.py --gpus 2` with no launcher starts its own two ranks."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full",
            "--transport", "gloo-host", "--width", "64", "--height", "120", "--reps", "8", "--exchange-check", "off",
            "--check"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=400)

@@ -76,8 +76,8 @@ def test_multiprocess_bands_one_gpu(pconv_mod, world, halo, fuse, preload, slots
                                          (2, ["--halo-select", "event"])])
 def test_bench_torchrun_rehearsal(world, extra):
     """bench.py under torch.distributed.run with `world` ranks sharing the one
-    GPU (gloo-host halos): the driver's N-GPU launch path with its default
-    oracle check (no --check flag: every BENCH line is self-verifying), every
+    GPU (gloo-host halos): the N-GPU launch path with --full and its default
+    oracle check (no --check flag: every --full line is self-verifying), every
     halo mode timed after the headline and compared with the CPU oracle."""
     import json
     import subprocess
@@ -86,7 +86,7 @@ def test_bench_torchrun_rehearsal(world, extra):
     port = _free_port()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
            "--master-addr", "127.0.0.1", f"--master-port={port}", os.path.join(ROOT, "bench.py"),
-           "--gpus", str(world), "--steps", "3", "--warmup", "1", "--transport", "gloo-host"] + extra
+           "--gpus", str(world), "--steps", "3", "--warmup", "1", "--full", "--transport", "gloo-host"] + extra
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=400)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -154,7 +154,7 @@ def test_bench_exchange_watchdog():
     port = _free_port()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr", "127.0.0.1", f"--master-port={port}", os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "3", "--warmup", "1", "--transport", "gloo-host", "--stall-exchange",
+           "--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--transport", "gloo-host", "--stall-exchange",
            "--watchdog", "8"]
     t0 = time.time()
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300)
@@ -249,7 +249,7 @@ def test_bench_emulated_rank_halo_modes(halo):
     import sys
 
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--emulate", "8:3", "--emulate-halo", halo,
-           "--steps", "10", "--warmup", "2"]
+           "--steps", "10", "--warmup", "2", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

@@ -5,10 +5,13 @@ pinned staging and tuned kernels between jobs; the client prints the
 reference's timing lines with its own end-to-end clock."""
 import json
 import os
+import shutil
 import socket
 import struct
 import subprocess
+import tempfile
 import time
+from pathlib import Path
 
 import numpy as np
 import pytest
@@ -33,9 +36,24 @@ def _request(sock, *args):
 
 
 @pytest.fixture
-def server(tmp_path, request):
+def sock_dir(tmp_path):
+    """Directory for a test's sockets.  A UNIX socket address holds at most
+    107 bytes of path (sockaddr_un.sun_path), and pytest's tmp_path under a
+    deep TMPDIR leaves no room for the socket's name: then a short-named
+    directory under /tmp takes its place."""
+    if len(str(tmp_path)) <= 80:
+        yield tmp_path
+        return
+    d = tempfile.mkdtemp(prefix="pconv-", dir="/tmp")
+    assert len(d) <= 80, d
+    yield Path(d)
+    shutil.rmtree(d, ignore_errors=True)
+
+
+@pytest.fixture
+def server(sock_dir, request):
     device = getattr(request, "param", -1)
-    sock = str(tmp_path / "pconv.sock")
+    sock = str(sock_dir / "pconv.sock")
     p = subprocess.Popen([CONV_BIN, "--serve", sock, "--device", str(device), "--idle-timeout", "300"],
                          stderr=subprocess.PIPE, text=True)
     for _ in range(600):
@@ -81,9 +99,9 @@ def test_service_errors_are_reported(server, tmp_path):
     assert _request(server, "__ping__")["ok"]  # the server survives bad jobs
 
 
-def test_client_without_server(tmp_path):
+def test_client_without_server(sock_dir):
     r = subprocess.run([CONV_BIN, "x.raw", "8", "8", "1", "grey", "--synthetic", "1", "--server",
-                        str(tmp_path / "none.sock")], capture_output=True, text=True, timeout=60)
+                        str(sock_dir / "none.sock")], capture_output=True, text=True, timeout=60)
     assert r.returncode != 0 and "conv --serve" in r.stderr
 
 
@@ -109,12 +127,12 @@ def test_service_gpu_jobs_reuse_engines(pconv_mod, server, tmp_path, rng):
     assert _request(server, "__ping__")["jobs"] == len(jobs)
 
 
-def test_python_service_client(pconv_mod, tmp_path, rng):
+def test_python_service_client(pconv_mod, tmp_path, sock_dir, rng):
     """pconv.utils.service: start a (CPU-only) server, run jobs through the
     Python client, errors raise ServiceError, shutdown stops the process."""
     from pconv.utils.service import ServiceClient, ServiceError, start_server
 
-    sock = str(tmp_path / "py.sock")
+    sock = str(sock_dir / "py.sock")
     p = start_server(sock, device=-1, idle_timeout=120)
     try:
         c = ServiceClient(sock)
@@ -135,11 +153,11 @@ def test_python_service_client(pconv_mod, tmp_path, rng):
     assert p.returncode == 0 and not os.path.exists(sock)
 
 
-def test_service_pool_distributes_jobs(pconv_mod, tmp_path, rng):
+def test_service_pool_distributes_jobs(pconv_mod, tmp_path, sock_dir, rng):
     """ServicePool over two CPU-only servers: every job exact, all jobs served."""
     from pconv.utils.service import ServicePool
 
-    pool = ServicePool.start([-1, -1], str(tmp_path / "pool"), idle_timeout=120)
+    pool = ServicePool.start([-1, -1], str(sock_dir / "pool"), idle_timeout=120)
     try:
         jobs, imgs = [], []
         for k in range(6):
@@ -158,10 +176,10 @@ def test_service_pool_distributes_jobs(pconv_mod, tmp_path, rng):
         pool.close()
 
 
-def test_serve_socket_path_safety(server, tmp_path):
+def test_serve_socket_path_safety(server, sock_dir):
     """`conv --serve PATH` never deletes a non-socket file at PATH, refuses a
     path a live server listens on, and replaces a dead server's socket."""
-    regular = tmp_path / "not_a_socket"
+    regular = sock_dir / "not_a_socket"
     regular.write_text("keep me")
     r = subprocess.run([CONV_BIN, "--serve", str(regular), "--device", "-1"], capture_output=True, text=True,
                        timeout=60)
@@ -170,7 +188,7 @@ def test_serve_socket_path_safety(server, tmp_path):
     r = subprocess.run([CONV_BIN, "--serve", server, "--device", "-1"], capture_output=True, text=True, timeout=60)
     assert r.returncode != 0 and "already listening" in r.stderr
     assert _request(server, "__ping__")["ok"]  # the live server is untouched
-    stale = str(tmp_path / "stale.sock")
+    stale = str(sock_dir / "stale.sock")
     s = socket.socket(socket.AF_UNIX)
     s.bind(stale)
     s.close()  # a socket file nobody listens on

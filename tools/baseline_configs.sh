@@ -22,8 +22,8 @@ run cli_1920x5040_rgb   60 $CONV x.raw 1920 5040 100 rgb --synthetic 1 --check -
 run cli_8192_rgb_100   120 $CONV x.raw 8192 8192 100 rgb --synthetic 1 --json --quiet --out /tmp/o4.raw
 run cli_32768_grey_200 180 $CONV x.raw 32768 32768 200 grey --synthetic 1 --json --quiet --out /tmp/o5.raw
 rm -f /tmp/o[0-5].raw
-run bench_1920x2520_rgb  120 python3 bench.py --steps 50 --warmup 10
-run bench_1920x2520_grey 120 python3 bench.py --channels grey --steps 50 --warmup 10
-run bench_8192_rgb_100   180 python3 bench.py --width 8192 --height 8192 --reps 100 --steps 10 --warmup 2
-run bench_32768_grey_200 300 python3 bench.py --width 32768 --height 32768 --channels grey --reps 200 --steps 3 --warmup 1 --slots 2
+run bench_1920x2520_rgb  120 python3 bench.py --full --steps 50 --warmup 10
+run bench_1920x2520_grey 120 python3 bench.py --full --channels grey --steps 50 --warmup 10
+run bench_8192_rgb_100   180 python3 bench.py --full --width 8192 --height 8192 --reps 100 --steps 10 --warmup 2
+run bench_32768_grey_200 300 python3 bench.py --full --width 32768 --height 32768 --channels grey --reps 200 --steps 3 --warmup 1 --slots 2
 echo "baseline configs done"

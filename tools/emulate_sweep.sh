@@ -10,7 +10,7 @@ for SPEC in $SPECS; do
     for F in ${FUSES:-auto 16}; do
       for C in ${CONC:-off on}; do
         fa=""; [ "$F" != auto ] && fa="--fuse $F"
-        line=$(timeout -k 5 120 python bench.py --emulate $SPEC --slots $S --concurrent $C $fa \
+        line=$(timeout -k 5 120 python bench.py --full --emulate $SPEC --slots $S --concurrent $C $fa \
                --steps $STEPS --warmup 40 --loop-steps 50 2>/dev/null | grep '^{')
         ms=$(echo "$line" | grep -oE '"ms_per_step": [0-9.]+' | head -1 | grep -oE '[0-9.]+$')
         lp=$(echo "$line" | grep -oE '"us_per_rep": [0-9.]+' | head -1 | grep -oE '[0-9.]+$')

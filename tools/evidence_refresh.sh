@@ -7,7 +7,7 @@ set -euo pipefail
 export TMPDIR=/tmp
 O=gpurun_out/refresh
 mkdir -p "$O"
-b() { local name=$1; shift; timeout -k 10 120 python3 -u bench.py "$@" > "$O/$name.json" 2> "$O/$name.err"; echo "$name: $(cut -c1-200 "$O/$name.json")"; }
+b() { local name=$1; shift; timeout -k 10 120 python3 -u bench.py --full "$@" > "$O/$name.json" 2> "$O/$name.err"; echo "$name: $(cut -c1-200 "$O/$name.json")"; }
 b bench_n1
 b emu_2_0 --emulate 2:0
 b emu_4_1 --emulate 4:1

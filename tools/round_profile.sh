@@ -8,10 +8,10 @@ export TMPDIR=/tmp
 O=gpurun_out/rprof
 mkdir -p "$O"
 SQ="SQ_WAVES SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_INSTS_LDS"
-timeout -k 10 120 python3 bench.py > "$O/bench_n1.json" 2> "$O/bench_n1.err"
+timeout -k 10 120 python3 bench.py --full > "$O/bench_n1.json" 2> "$O/bench_n1.err"
 echo "bench: $(cut -c1-160 "$O/bench_n1.json")"
 timeout -k 10 180 rocprofv3 --kernel-trace --memory-copy-trace --stats --output-format csv -d "$O/trace_bench" -o run \
-  -- python3 bench.py --steps 50 --warmup 10 --loop-steps 50 > "$O/trace_bench.log" 2>&1
+  -- python3 bench.py --full --steps 50 --warmup 10 --loop-steps 50 > "$O/trace_bench.log" 2>&1
 echo "trace done"
 timeout -s KILL 120 rocprofv3 --kernel-trace --output-format csv -d "$O/pmc_rgb" -o run --pmc $SQ GRBM_GUI_ACTIVE \
   -- python3 tools/kernel_sweep.py --width 1920 --height 2520 --channels rgb --reps 40 --fuse 8 --rounds 1 --iters 5 \
