@@ -32,6 +32,7 @@ struct CliConfig {
   Backend backend = Backend::Hip;
   int gpus = 1;
   std::string filter = "gaussian";
+  Border border = Border::Zero;  // --border: rule at the global image's edges (every backend)
   int halo = 0;   // 0 = auto
   int fuse = 0;   // 0 = auto
   bool overlap = true;

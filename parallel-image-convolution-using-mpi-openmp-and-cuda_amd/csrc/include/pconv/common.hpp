@@ -26,6 +26,15 @@ inline int channel_count(Channels c) { return static_cast<int>(c); }
 const char* channels_name(Channels c);
 Channels parse_channels(const std::string& s);  // "grey" | "rgb" | "rgba"
 
+// What a tap reads outside the GLOBAL image (a band edge that is not an image
+// edge is no border).  Zero: the reference's zero padding, the default and the
+// parity contract.  Replicate: the nearest image pixel, i.e.
+// in[clamp(y, 0, H-1)][clamp(x, 0, W-1)] — a repeated blur then keeps its
+// brightness at the frame instead of mixing zeros into the outer pixels.
+enum class Border : int { Zero = 0, Replicate = 1 };
+const char* border_name(Border b);
+Border parse_border(const std::string& s);  // "zero" | "replicate"
+
 // Thrown by every layer.  `what()` carries "[rank R] where: message".
 class Error : public std::runtime_error {
  public:

@@ -26,21 +26,29 @@ enum class CpuBackend { Serial, OpenMP };
 // One step: for owned rows [r0, r1) of the frame, dst = conv(src).  Pixels whose
 // global row lies outside [0, image_height) are treated as zero by the caller's
 // frame (ghost rows hold zeros at the global image edges).
+// With Border::Replicate the taps clamp to the global image instead (g_row0 =
+// global row of frame row 0, height = global image height, < 0: the frame's
+// owned rows end the image): [r0, r1) must lie inside the image, ghost rows
+// and pad columns beyond it are never read and the source frame is not
+// modified.
 void cpu_step(const Filter& f, Channels ch, const FrameLayout& lay, const uint8_t* src_frame,
-              uint8_t* dst_frame, int64_t r0, int64_t r1, CpuBackend be);
+              uint8_t* dst_frame, int64_t r0, int64_t r1, CpuBackend be, Border border = Border::Zero,
+              int64_t g_row0 = 0, int64_t height = -1);
 
 // Reference semantics of one fused launch (what the temporal GPU kernel
 // computes): `steps` repetitions starting from src rows [lo-steps, hi+steps),
-// rows outside the global image [0, height) held at zero after every step;
-// writes rows [lo, hi) of dst only.  g_row0 = global row of frame row 0.
+// rows outside the global image [0, height) held at zero after every step
+// (Border::Zero) or never read (Border::Replicate, whatever the frame holds
+// there); writes rows [lo, hi) of dst only.  g_row0 = global row of frame row 0.
 void cpu_fused_launch(const Filter& f, Channels ch, const FrameLayout& lay, const uint8_t* src_frame,
                       uint8_t* dst_frame, int64_t lo, int64_t hi, int steps, int64_t g_row0, int64_t height,
-                      CpuBackend be);
+                      CpuBackend be, Border border = Border::Zero);
 
-// reps steps on a contiguous image (pitch == row_bytes), zero-padded semantics.
+// reps steps on a contiguous image (pitch == row_bytes), zero-padded semantics
+// unless `border` says otherwise.
 // Ping-pongs internally; result written to `out` (may alias `in`).
 void cpu_convolve(const Filter& f, const ImageGeom& geom, const uint8_t* in, uint8_t* out,
-                  int reps, CpuBackend be, int threads = 0);
+                  int reps, CpuBackend be, int threads = 0, Border border = Border::Zero);
 
 // OpenMP team size when the user set none (OMP_NUM_THREADS unset, no
 // --threads): the CPUs this process may run on (affinity mask), capped by the

@@ -62,6 +62,10 @@ struct EngineOptions {
   // reference's Isend/Irecv + inner compute + Wait + edges, one graph).
   bool capture_exchanges = false;
   KernelVariant variant = KernelVariant::Auto;
+  // Rule at the global image's edges, applied by every launch of the engine
+  // (tuning launches included).  Replicate needs no extra ghost rows: the
+  // planner and the frames are the zero border's.
+  Border border = Border::Zero;
   // Borrowed streams (nullptr: the engine creates its own).  A process has
   // few hardware queues (GPU_MAX_HW_QUEUES, 4 by default); pipeline slots
   // share streams so that unrelated streams never alias one queue.

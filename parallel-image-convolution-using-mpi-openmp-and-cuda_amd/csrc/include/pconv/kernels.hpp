@@ -38,6 +38,10 @@ struct StencilLaunch {
   int steps = 1;                 // fused repetitions (temporal blocking) in this launch
   int64_t g_row0 = 0;            // global image row of frame row 0
   int64_t height = 0;            // global image height (rows outside are zero each step)
+  // Rule at the global image's edges.  Replicate is built into the temporal
+  // kernels only (they apply it at every fused step): Auto routes every step
+  // count to them, the single-step variants reject it.
+  Border border = Border::Zero;
 };
 
 enum class KernelVariant : int {

@@ -292,8 +292,10 @@ void prepare_stencil(const Filter& f, Channels ch, const StencilLaunch& a_in, hi
   a.r0 = std::max(a.r0, -a.g_row0);
   a.r1 = std::min(a.r1, a.height - a.g_row0);
   if (a.r1 <= a.r0) return;
-  if (v == KernelVariant::Auto && f.binomial121 && a.steps > 1) v = KernelVariant::Temporal;
-  if (v == KernelVariant::Auto && !f.binomial121 && a.steps > 1) v = KernelVariant::FloatTemporal;
+  // a non-zero border exists in the temporal kernels only: every step count goes there
+  const bool fused = a.steps > 1 || a.border != Border::Zero;
+  if (v == KernelVariant::Auto && f.binomial121 && fused) v = KernelVariant::Temporal;
+  if (v == KernelVariant::Auto && !f.binomial121 && fused) v = KernelVariant::FloatTemporal;
   if (v == KernelVariant::Temporal && f.binomial121 && a.steps <= kMaxFusedSteps) prepare_swar(a, ch, stream);
   if (v == KernelVariant::FloatTemporal && a.steps <= kMaxFusedSteps) prepare_float_temporal(f, ch, a, stream);
 }
@@ -315,10 +317,17 @@ void launch_stencil(const Filter& f, Channels ch, const StencilLaunch& a_in, hip
               "launch_stencil: pitch too small for 16-byte vector access");
   PCONV_CHECK(a.row_bytes < (int64_t(1) << 31) && a.r1 - a.frame_lo < (int64_t(1) << 31),
               "launch_stencil: geometry exceeds 32-bit kernel indices");
+  // The single-step kernels take their boundary from the frame's zero pad: a
+  // non-zero border runs on the temporal kernels for every step count (an
+  // int_exact filter is bit-identical in the float kernel by definition).
+  const bool fused = a.steps > 1 || a.border != Border::Zero;
   if (v == KernelVariant::Auto)
-    v = f.binomial121 ? (a.steps > 1 ? KernelVariant::Temporal : KernelVariant::Binomial)
-                      : (a.steps > 1 ? KernelVariant::FloatTemporal
-                                     : (f.int_exact ? KernelVariant::Int9 : KernelVariant::Float9));
+    v = f.binomial121 ? (fused ? KernelVariant::Temporal : KernelVariant::Binomial)
+                      : (fused ? KernelVariant::FloatTemporal
+                               : (f.int_exact ? KernelVariant::Int9 : KernelVariant::Float9));
+  PCONV_CHECK(a.border == Border::Zero || v == KernelVariant::Temporal || v == KernelVariant::FloatTemporal,
+              "launch_stencil: border '" + std::string(border_name(a.border)) + "' not supported by kernel '" +
+                  std::string(kernel_variant_name(v)) + "' (temporal and float_temporal only)");
   if (v == KernelVariant::FloatTemporal) {
     launch_float_temporal(f, ch, a, stream);
     PCONV_HIP_CHECK(hipGetLastError());

@@ -11,7 +11,9 @@
 // separate multiply and add (no contraction: the TU is built with
 // -ffp-contract=off; products and sums are packed f32 ops, one rounding each),
 // row-major tap order, truncation after EVERY step, zero outside the image at
-// every step.  UNIFORM filters (all nine weights equal, e.g. box) compute each
+// every step (Border::Zero) or the nearest image pixel (Border::Replicate: the
+// out-of-image OPERAND is substituted, never a correction term added — float
+// sums depend on their order).  UNIFORM filters (all nine weights equal, e.g. box) compute each
 // input byte's product once per row instead of once per tap: fl(p * w) does
 // not depend on the tap, so the chain of additions is unchanged.
 //
@@ -53,10 +55,23 @@ __device__ __forceinline__ float ub(u32 x, int k) { return static_cast<float>((x
 // -ffp-contract=off, so a product never fuses into the following add.
 typedef float f2 __attribute__((ext_vector_type(2)));
 
+// Replicate border, columns: what a lane of a strip that touches the image's
+// left or right edge substitutes in its window e[0, 8 + 2 CH) (byte columns
+// x - CH + t): in the lane holding column 0 the CH entries before it take the
+// first pixel's bytes (e[t] = e[t + CH]); the CH entries from window index
+// `nin` on — the first byte columns past the row — take the last pixel's
+// (e[t] = e[t - CH]; they sit in the window of the lane holding the row's last
+// byte and, when that pixel straddles two lanes, of the lane before it).
+struct ColFix {
+  bool left;  // this lane holds byte column 0
+  int nin;    // window entries before the row's end: row_bytes - (x - CH)
+};
+
 // Row (8 bytes per lane) -> pairs E[j] = (byte j - CH, byte j + 4 - CH) for
-// j in [0, 4 + 2 CH): bytes [-CH, 8 + CH) of the row (times w when UNIFORM).
-template <int CH, bool UNIFORM>
-__device__ __forceinline__ void expand(const u32 (&X)[2], float w, f2 (&E)[4 + 2 * CH]) {
+// j in [0, 4 + 2 CH): bytes [-CH, 8 + CH) of the row (times w when UNIFORM:
+// fl(p * w) of a substituted byte is the same product).
+template <int CH, bool UNIFORM, bool REP = false>
+__device__ __forceinline__ void expand(const u32 (&X)[2], float w, f2 (&E)[4 + 2 * CH], const ColFix* cf = nullptr) {
   const u32 l = __builtin_amdgcn_mov_dpp(X[1], 0x138, 0xf, 0xf, true);  // wave_shr:1 -> left lane's bytes 4..7
   const u32 r = __builtin_amdgcn_mov_dpp(X[0], 0x130, 0xf, 0xf, true);  // wave_shl:1 -> right lane's bytes 0..3
   float e[8 + 2 * CH];
@@ -66,6 +81,13 @@ __device__ __forceinline__ void expand(const u32 (&X)[2], float w, f2 (&E)[4 + 2
   for (int j = 0; j < 8; ++j) e[CH + j] = ub(X[j >> 2], j & 3);
 #pragma unroll
   for (int j = 0; j < CH; ++j) e[CH + 8 + j] = ub(r, j);
+  if constexpr (REP) {
+#pragma unroll
+    for (int t = 0; t < CH; ++t) e[t] = cf->left ? e[t + CH] : e[t];
+    // ascending t reads e[t - CH] before the right edge: never a substituted entry
+#pragma unroll
+    for (int t = CH; t < 8 + 2 * CH; ++t) e[t] = (t >= cf->nin && t < cf->nin + CH) ? e[t - CH] : e[t];
+  }
 #pragma unroll
   for (int j = 0; j < 4 + 2 * CH; ++j) E[j] = (f2){e[j], e[j + 4]};
   if constexpr (UNIFORM) {
@@ -113,7 +135,134 @@ __device__ __forceinline__ f2 out_pair(const f2 (&a)[4 + 2 * CH], const f2 (&b)[
   return (f2){__builtin_truncf(acc.x), __builtin_truncf(acc.y)};
 }
 
-template <int CH, bool UNIFORM, int M, int NW>
+// Replicate state of a lane / wave; the zero border carries nothing.
+template <bool REP>
+struct RepState {};
+template <>
+struct RepState<true> {
+  ColFix cf;
+  bool above_own, below_own;  // global row 0 / the last image row is this wave's first / last register row
+};
+
+// Replicate border, rows inside one wave (as edge_rows of the SWAR kernel):
+// the register row just above global row 0 takes row 0's bytes, the one just
+// below the last image row that row's.  After the load and after every step's
+// re-zeroing, only in waves that hold out-of-image rows (zero on entry: the
+// copy is an OR under a wave-uniform mask, no dynamic register indexing).
+template <int M>
+__device__ __forceinline__ void edge_rows_ft(u32 (&D)[M][2], int out_top, int out_bot) {
+  out_top = __builtin_amdgcn_readfirstlane(out_top);  // wave-uniform by construction
+  out_bot = __builtin_amdgcn_readfirstlane(out_bot);
+  asm volatile("" : "+s"(out_top), "+s"(out_bot));  // masks recomputed per call, not kept live across the steps
+#pragma unroll
+  for (int i = 0; i + 1 < M; ++i) {
+    const u32 take = i + 1 == out_top ? 0xffffffffu : 0u;
+    D[i][0] |= D[i + 1][0] & take;
+    D[i][1] |= D[i + 1][1] & take;
+  }
+#pragma unroll
+  for (int i = M - 1; i >= 1; --i) {
+    const u32 take = i == out_bot ? 0xffffffffu : 0u;
+    D[i][0] |= D[i - 1][0] & take;
+    D[i][1] |= D[i - 1][1] & take;
+  }
+}
+
+// The `steps` repetitions of a wave's M register rows.  COLFIX (replicate
+// border, strips that touch the image's left or right edge) substitutes the
+// out-of-image columns of every expanded row; it is a template parameter, so
+// that the other strips run the loop without a single select — as a run-time
+// branch inside expand() it made the compiler spill (256 VGPRs + 214 spilled on
+// k_float_temporal<3, true, 16, 8>).
+template <int CH, bool UNIFORM, int M, int NW, bool REP, bool COLFIX>
+__device__ __forceinline__ void ft_steps(u32 (&D)[M][2], uint2 (&lds)[2][NW][2][64], int steps, int w, int lane,
+                                         float w0, const f2 (&wv)[9], bool edge_strip, u32 m0, u32 m1, int out_top,
+                                         int out_bot, const RepState<REP>& rs) {
+  for (int s = 0; s < steps; ++s) {
+    const int par = s & 1;
+    lds[par][w][0][lane] = make_uint2(D[0][0], D[0][1]);
+    lds[par][w][1][lane] = make_uint2(D[M - 1][0], D[M - 1][1]);
+    __syncthreads();
+    u32 A[2], B[2];
+    {
+      int wa = w > 0 ? w - 1 : 0;
+      int wb = w < NW - 1 ? w + 1 : w;
+      int sa = 1, sb = 0;
+      if constexpr (REP) {
+        // the row above global row 0 is row 0 itself, the row below the last
+        // image row is that row: this wave's own published boundary row
+        if (rs.above_own) {
+          wa = w;
+          sa = 0;
+        }
+        if (rs.below_own) {
+          wb = w;
+          sb = 1;
+        }
+      }
+      const uint2 a = lds[par][wa][sa][lane], b = lds[par][wb][sb][lane];
+      A[0] = a.x;
+      A[1] = a.y;
+      B[0] = b.x;
+      B[1] = b.y;
+    }
+    f2 ea[4 + 2 * CH], eb[4 + 2 * CH], ec[4 + 2 * CH];
+    if constexpr (COLFIX) {
+      expand<CH, UNIFORM, true>(A, w0, ea, &rs.cf);
+      expand<CH, UNIFORM, true>(D[0], w0, eb, &rs.cf);
+    } else {
+      expand<CH, UNIFORM>(A, w0, ea);
+      expand<CH, UNIFORM>(D[0], w0, eb);
+    }
+#pragma unroll
+    for (int i = 0; i < M; ++i) {
+      if constexpr (COLFIX) {
+        if (i + 1 < M)
+          expand<CH, UNIFORM, true>(D[i + 1], w0, ec, &rs.cf);
+        else
+          expand<CH, UNIFORM, true>(B, w0, ec, &rs.cf);
+      } else {
+        if (i + 1 < M)
+          expand<CH, UNIFORM>(D[i + 1], w0, ec);
+        else
+          expand<CH, UNIFORM>(B, w0, ec);
+      }
+      u32 o0 = 0, o1 = 0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const f2 v = out_pair<CH, UNIFORM>(ea, eb, ec, j, wv);
+        o0 = __builtin_amdgcn_cvt_pk_u8_f32(v.x, j, o0);
+        o1 = __builtin_amdgcn_cvt_pk_u8_f32(v.y, j, o1);
+      }
+      D[i][0] = o0;
+      D[i][1] = o1;
+#pragma unroll
+      for (int j = 0; j < 4 + 2 * CH; ++j) {
+        ea[j] = eb[j];
+        eb[j] = ec[j];
+      }
+    }
+    if (edge_strip) {
+#pragma unroll
+      for (int i = 0; i < M; ++i) {
+        D[i][0] &= m0;
+        D[i][1] &= m1;
+      }
+    }
+    if (out_top > 0 || out_bot < M) {
+#pragma unroll
+      for (int i = 0; i < M; ++i)
+        if (i < out_top || i >= out_bot) {
+          D[i][0] = 0;
+          D[i][1] = 0;
+        }
+      if constexpr (REP) edge_rows_ft<M>(D, out_top, out_bot);
+    }
+  }
+
+}
+
+template <int CH, bool UNIFORM, int M, int NW, bool REP = false>
 __global__ __launch_bounds__(64 * NW) void k_float_temporal(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
                                                             int64_t pitch, int row_bytes, int r0, int r1, int steps,
                                                             int g_row0, int height, FloatTaps tp) {
@@ -156,60 +305,79 @@ __global__ __launch_bounds__(64 * NW) void k_float_temporal(const uint8_t* __res
   }
   const int out_top = min(max(-g_row0 - row_base, 0), M);
   const int out_bot = min(max(height - g_row0 - row_base, 0), M);
+  // replicate: column substitution state, and the register rows holding the
+  // image's first / last row (wave-uniform; outside [0, M) when not in this wave)
+  RepState<REP> rs;
+  if constexpr (REP) {
+    rs.cf = ColFix{x == 0, row_bytes - (x - CH)};
+    rs.above_own = -g_row0 - row_base == 0;
+    rs.below_own = height - 1 - g_row0 - row_base == M - 1;
+    if (out_top > 0 || out_bot < M) edge_rows_ft<M>(D, out_top, out_bot);  // the loaded rows' out-of-image neighbours
+  }
 
-  for (int s = 0; s < steps; ++s) {
-    const int par = s & 1;
-    lds[par][w][0][lane] = make_uint2(D[0][0], D[0][1]);
-    lds[par][w][1][lane] = make_uint2(D[M - 1][0], D[M - 1][1]);
-    __syncthreads();
-    u32 A[2], B[2];
-    {
-      const int wa = w > 0 ? w - 1 : 0;
-      const int wb = w < NW - 1 ? w + 1 : w;
-      const uint2 a = lds[par][wa][1][lane], b = lds[par][wb][0][lane];
-      A[0] = a.x;
-      A[1] = a.y;
-      B[0] = b.x;
-      B[1] = b.y;
-    }
-    f2 ea[4 + 2 * CH], eb[4 + 2 * CH], ec[4 + 2 * CH];
-    expand<CH, UNIFORM>(A, w0, ea);
-    expand<CH, UNIFORM>(D[0], w0, eb);
-#pragma unroll
-    for (int i = 0; i < M; ++i) {
-      if (i + 1 < M)
-        expand<CH, UNIFORM>(D[i + 1], w0, ec);
-      else
-        expand<CH, UNIFORM>(B, w0, ec);
-      u32 o0 = 0, o1 = 0;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const f2 v = out_pair<CH, UNIFORM>(ea, eb, ec, j, wv);
-        o0 = __builtin_amdgcn_cvt_pk_u8_f32(v.x, j, o0);
-        o1 = __builtin_amdgcn_cvt_pk_u8_f32(v.y, j, o1);
+  if constexpr (REP) {
+    if (edge_strip)
+      ft_steps<CH, UNIFORM, M, NW, true, true>(D, lds, steps, w, lane, w0, wv, edge_strip, m0, m1, out_top, out_bot, rs);
+    else
+      ft_steps<CH, UNIFORM, M, NW, true, false>(D, lds, steps, w, lane, w0, wv, edge_strip, m0, m1, out_top, out_bot,
+                                                rs);
+  } else {
+    // The zero border's loop, inline as it always was (routed through
+    // ft_steps the compiler allocates its registers differently).
+    for (int s = 0; s < steps; ++s) {
+      const int par = s & 1;
+      lds[par][w][0][lane] = make_uint2(D[0][0], D[0][1]);
+      lds[par][w][1][lane] = make_uint2(D[M - 1][0], D[M - 1][1]);
+      __syncthreads();
+      u32 A[2], B[2];
+      {
+        const int wa = w > 0 ? w - 1 : 0;
+        const int wb = w < NW - 1 ? w + 1 : w;
+        const uint2 a = lds[par][wa][1][lane], b = lds[par][wb][0][lane];
+        A[0] = a.x;
+        A[1] = a.y;
+        B[0] = b.x;
+        B[1] = b.y;
       }
-      D[i][0] = o0;
-      D[i][1] = o1;
-#pragma unroll
-      for (int j = 0; j < 4 + 2 * CH; ++j) {
-        ea[j] = eb[j];
-        eb[j] = ec[j];
-      }
-    }
-    if (edge_strip) {
-#pragma unroll
+      f2 ea[4 + 2 * CH], eb[4 + 2 * CH], ec[4 + 2 * CH];
+      expand<CH, UNIFORM>(A, w0, ea);
+      expand<CH, UNIFORM>(D[0], w0, eb);
+  #pragma unroll
       for (int i = 0; i < M; ++i) {
-        D[i][0] &= m0;
-        D[i][1] &= m1;
-      }
-    }
-    if (out_top > 0 || out_bot < M) {
-#pragma unroll
-      for (int i = 0; i < M; ++i)
-        if (i < out_top || i >= out_bot) {
-          D[i][0] = 0;
-          D[i][1] = 0;
+        if (i + 1 < M)
+          expand<CH, UNIFORM>(D[i + 1], w0, ec);
+        else
+          expand<CH, UNIFORM>(B, w0, ec);
+        u32 o0 = 0, o1 = 0;
+  #pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const f2 v = out_pair<CH, UNIFORM>(ea, eb, ec, j, wv);
+          o0 = __builtin_amdgcn_cvt_pk_u8_f32(v.x, j, o0);
+          o1 = __builtin_amdgcn_cvt_pk_u8_f32(v.y, j, o1);
         }
+        D[i][0] = o0;
+        D[i][1] = o1;
+  #pragma unroll
+        for (int j = 0; j < 4 + 2 * CH; ++j) {
+          ea[j] = eb[j];
+          eb[j] = ec[j];
+        }
+      }
+      if (edge_strip) {
+  #pragma unroll
+        for (int i = 0; i < M; ++i) {
+          D[i][0] &= m0;
+          D[i][1] &= m1;
+        }
+      }
+      if (out_top > 0 || out_bot < M) {
+  #pragma unroll
+        for (int i = 0; i < M; ++i)
+          if (i < out_top || i >= out_bot) {
+            D[i][0] = 0;
+            D[i][1] = 0;
+          }
+      }
     }
   }
 
@@ -284,7 +452,9 @@ void launch_ft_shape(const StencilLaunch& a, const FloatTaps& tp, hipStream_t s)
   PCONV_CHECK(vlanes > 0 && vrows > 0, "float temporal kernel: steps too large for the tile");
   const int nchunks = static_cast<int>(ceil_div<int64_t>(a.row_bytes, 8));
   const dim3 grid(ceil_div(nchunks, vlanes), ceil_div(static_cast<int>(a.r1 - a.r0), vrows));
-  k_float_temporal<CH, UNIFORM, M, NW><<<grid, dim3(64 * NW), 0, s>>>(
+  const auto kern = a.border == Border::Replicate ? &k_float_temporal<CH, UNIFORM, M, NW, true>
+                                                  : &k_float_temporal<CH, UNIFORM, M, NW, false>;
+  kern<<<grid, dim3(64 * NW), 0, s>>>(
       a.src, a.dst, a.pitch, static_cast<int>(a.row_bytes), static_cast<int>(a.r0), static_cast<int>(a.r1), steps,
       static_cast<int>(a.g_row0), static_cast<int>(std::min<int64_t>(a.height, int64_t(1) << 30)), tp);
 }

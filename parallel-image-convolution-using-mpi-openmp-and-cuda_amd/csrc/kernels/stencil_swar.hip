@@ -32,6 +32,11 @@
 // one row / CH bytes per step and is absorbed by a `steps`-row / ceil(steps*
 // CH/LW)-lane halo; rows and columns outside the image are forced to zero
 // after every step (zero-padding semantics of mpi/mpi_convolution.c:111-118).
+// The replicate border (template parameter REP) keeps those zeros except in
+// the one row above and below the image, which take the edge row's values, and
+// adds the edge columns' fields once more to the horizontal sums of edge tiles
+// (swar_device.hpp, EdgeFix); REP = false instantiates exactly the zero-border
+// kernel.
 // Tile shape (LW, M, NW) comes from a latency model of one launch (see
 // swar_launch_cycles) — big images get the least redundant tile, small bands
 // (the 8-GPU split of a small image) get small tiles spread over all CUs.
@@ -64,23 +69,47 @@ namespace {
 // ghost row per side recomputed) never won a tuning and forced it measured
 // 0-8 % slower than form 1 (round 5: headline 3.645 vs 3.377 us/rep,
 // 32768^2 grey 113.8 vs 109.2; profiles/r05/d/form_ab.jsonl): removed.
-template <int CH, int NP, int M, int NW, int FORM>
+template <int CH, int NP, int M, int NW, int FORM, bool REP>
 __device__ __forceinline__ void run_steps(u32 (&D)[M][NP], uint4 (&lds)[2][NW][2][NP / 4][64], int steps, int w,
-                                          int lane, bool needs_mask, const u32 (&cm)[NP], int out_top, int out_bot) {
+                                          int lane, bool needs_mask, const u32 (&cm)[NP], int out_top, int out_bot,
+                                          const EdgeFix<CH, NP, REP>& ef) {
+  if constexpr (REP)
+    if (out_top > 0 || out_bot < M) edge_rows<NP, M>(D, out_top, out_bot);  // the loaded rows' out-of-image neighbours
   if constexpr (FORM == 1) {
     int s = 0;
     for (; s + 2 <= steps; s += 2) {
-      swar_step<CH, NP, M, NW, 1>(D, lds, 0, w, lane, needs_mask, cm, out_top, out_bot);
-      swar_step<CH, NP, M, NW, 2>(D, lds, 1, w, lane, needs_mask, cm, out_top, out_bot);
+      swar_step<CH, NP, M, NW, 1, REP>(D, lds, 0, w, lane, needs_mask, cm, out_top, out_bot, ef);
+      swar_step<CH, NP, M, NW, 2, REP>(D, lds, 1, w, lane, needs_mask, cm, out_top, out_bot, ef);
     }
-    if (s < steps) swar_step<CH, NP, M, NW, 0>(D, lds, 0, w, lane, needs_mask, cm, out_top, out_bot);
+    if (s < steps) swar_step<CH, NP, M, NW, 0, REP>(D, lds, 0, w, lane, needs_mask, cm, out_top, out_bot, ef);
   } else {
     for (int s = 0; s < steps; ++s)
-      swar_step<CH, NP, M, NW, 0>(D, lds, s & 1, w, lane, needs_mask, cm, out_top, out_bot);
+      swar_step<CH, NP, M, NW, 0, REP>(D, lds, s & 1, w, lane, needs_mask, cm, out_top, out_bot, ef);
   }
 }
 
-template <int CH, int LW, int M, int NW, int FORM>
+// The replicate border's per-lane state (swar_device.hpp, EdgeFix) for a tile
+// whose strips start at byte columns baseA / baseB and whose wave's register
+// row 0 is frame row row_base.  `h` is set only in tiles that hold the image's
+// first or last pixel of a row, above_own / below_own only in the wave whose
+// first / last register row is the image's first / last row: interior tiles
+// skip every correction on uniform branches.
+template <int CH, int NP, int M>
+__device__ __forceinline__ void edge_fix(EdgeFix<CH, NP, true>& ef, int baseA, int baseB, bool hasB, int lane,
+                                         int row_bytes, int row_base, int g_row0, int height) {
+  constexpr int LW = NP;
+  edge_masks<CH, NP>(ef, baseA + lane * LW, baseB + lane * LW, hasB, row_bytes);
+  const auto holds_edge = [&](int base) {
+    return base <= 0 || (base < row_bytes && base + 64 * LW > row_bytes - CH);
+  };
+  ef.h = holds_edge(baseA) || (hasB && holds_edge(baseB));
+  ef.above_own = -g_row0 - row_base == 0;
+  ef.below_own = height - 1 - g_row0 - row_base == M - 1;
+}
+template <int CH, int NP, int M>
+__device__ __forceinline__ void edge_fix(EdgeFix<CH, NP, false>&, int, int, bool, int, int, int, int, int) {}
+
+template <int CH, int LW, int M, int NW, int FORM, bool REP = false>
 __global__ __launch_bounds__(64 * NW) void k_swar(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
                                                   int64_t pitch, int row_bytes, int r0, int r1,
                                                   int steps, int g_row0, int height, int nstrips, int pair_stride,
@@ -136,7 +165,10 @@ __global__ __launch_bounds__(64 * NW) void k_swar(const uint8_t* __restrict__ sr
   const int out_top = min(max(-g_row0 - row_base, 0), M);
   const int out_bot = min(max(height - g_row0 - row_base, 0), M);
 
-  run_steps<CH, NP, M, NW, FORM>(D, lds, steps, w, lane, needs_mask, cm, out_top, out_bot);
+  EdgeFix<CH, NP, REP> ef;
+  edge_fix<CH, NP, M>(ef, baseA, baseB, hasB, lane, row_bytes, row_base, g_row0, height);
+
+  run_steps<CH, NP, M, NW, FORM, REP>(D, lds, steps, w, lane, needs_mask, cm, out_top, out_bot, ef);
 
   const bool lane_in = lane >= hl && lane < 64 - hl;
   const bool stA = lane_in && validA > 0, stB = lane_in && validB > 0;
@@ -179,7 +211,7 @@ __global__ __launch_bounds__(64 * NW) void k_swar(const uint8_t* __restrict__ sr
 // in docs/PERFORMANCE.md).
 //   Contract (checked at launch): row_bytes % 4 == 0, source and destination
 // ranges under 2 GiB.
-template <int CH, int M, int NW, int FORM>
+template <int CH, int M, int NW, int FORM, bool REP = false>
 __global__ __launch_bounds__(64 * NW) void k_swar_pf(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
                                                      int pitch, int row_bytes, int r0, int r1,
                                                      int steps, int g_row0, int height, int nstrips, int pair_stride,
@@ -232,7 +264,9 @@ __global__ __launch_bounds__(64 * NW) void k_swar_pf(const uint8_t* __restrict__
     cm[k] = (xA >= 0 && xA + k < row_bytes ? 0xffffu : 0u) | (xB >= 0 && xB + k < row_bytes ? 0xffff0000u : 0u);
   const int out_top = min(max(-g_row0 - row_base, 0), M);
   const int out_bot = min(max(height - g_row0 - row_base, 0), M);
-  run_steps<CH, NP, M, NW, FORM>(D, lds, steps, w, lane, needs_mask, cm, out_top, out_bot);
+  EdgeFix<CH, NP, REP> ef;
+  edge_fix<CH, NP, M>(ef, baseA, baseB, sB < nstrips, lane, row_bytes, row_base, g_row0, height);
+  run_steps<CH, NP, M, NW, FORM, REP>(D, lds, steps, w, lane, needs_mask, cm, out_top, out_bot, ef);
   const bool lane_in = lane >= hl && lane < 64 - hl;
   const int tile_r0 = row_base + steps - w * M;
   const int st_lo = max(tile_r0, r0), st_hi = min(tile_r0 + vrows, st_end);
@@ -276,16 +310,22 @@ int alt_mode() { return g_alt_mode.load(std::memory_order_relaxed); }
 // form is faster in most measured geometries.
 int default_form() { return alt_mode() >= 0 ? alt_mode() : 1; }
 
-// Kernel of one step form.
+// Kernel of one step form and border rule (the border is a template
+// parameter: the zero-border instantiations are the kernels they always were).
 template <int CH, int LW, int M, int NW>
-auto swar_kernel(int form) {
+auto swar_kernel(int form, Border border = Border::Zero) {
   using F = decltype(&k_swar<CH, LW, M, NW, 0>);
+  if (border == Border::Replicate)
+    return form >= 1 ? static_cast<F>(&k_swar<CH, LW, M, NW, 1, true>)
+                     : static_cast<F>(&k_swar<CH, LW, M, NW, 0, true>);
   return form >= 1 ? static_cast<F>(&k_swar<CH, LW, M, NW, 1>) : static_cast<F>(&k_swar<CH, LW, M, NW, 0>);
 }
 
 template <int CH, int M, int NW>
-auto swar_pf_kernel(int form) {
+auto swar_pf_kernel(int form, Border border = Border::Zero) {
   using F = decltype(&k_swar_pf<CH, M, NW, 0>);
+  if (border == Border::Replicate)
+    return form >= 1 ? static_cast<F>(&k_swar_pf<CH, M, NW, 1, true>) : static_cast<F>(&k_swar_pf<CH, M, NW, 0, true>);
   return form >= 1 ? static_cast<F>(&k_swar_pf<CH, M, NW, 1>) : static_cast<F>(&k_swar_pf<CH, M, NW, 0>);
 }
 
@@ -301,7 +341,7 @@ void launch_one(const StencilLaunch& a, hipStream_t s, int form) {
   const int row_tiles = ceil_div(static_cast<int>(a.r1 - a.r0), vrows);
   const dim3 grid(pair_stride * row_tiles);
   const int64_t hmax = std::min<int64_t>(a.height, int64_t(1) << 30);
-  swar_kernel<CH, LW, M, NW>(form)<<<grid, dim3(64 * NW), 0, s>>>(
+  swar_kernel<CH, LW, M, NW>(form, a.border)<<<grid, dim3(64 * NW), 0, s>>>(
       a.src, a.dst, a.pitch, static_cast<int>(a.row_bytes),
       static_cast<int>(a.r0), static_cast<int>(a.r1), steps, static_cast<int>(a.g_row0), static_cast<int>(hmax), nstrips,
       pair_stride, row_tiles, xcd_swizzle_enabled() ? 1 : 0);
@@ -376,7 +416,7 @@ void launch_pf_one(const StencilLaunch& a, hipStream_t s, int form) {
   const int grid = static_cast<int>(ntiles);
   const int xs = xcd_swizzle_enabled() ? 1 : 0;
   const int hmax = static_cast<int>(std::min<int64_t>(a.height, int64_t(1) << 30));
-  swar_pf_kernel<CH, M, NW>(form)<<<dim3(grid), dim3(64 * NW), 0, s>>>(
+  swar_pf_kernel<CH, M, NW>(form, a.border)<<<dim3(grid), dim3(64 * NW), 0, s>>>(
       a.src, a.dst, static_cast<int>(a.pitch), static_cast<int>(a.row_bytes), static_cast<int>(a.r0),
       static_cast<int>(a.r1), steps, static_cast<int>(a.g_row0), hmax, nstrips, pair_stride, row_tiles, xs);
 }

@@ -77,6 +77,56 @@ __device__ __forceinline__ void horiz(const u32 (&X)[NP], u32 (&H)[NP]) {
   for (int k = 0; k < NP; ++k) H[k] = keep(k >= CH ? P[k - CH] + P[k] : xlane<-1>(P[k - CH + NP]) + P[k]);
 }
 
+// Replicate border (Border::Replicate): what one lane needs to turn the
+// zero-padded sums into edge-replicated ones.  Out-of-image fields are held at
+// zero, so the clamped tap is the zero-padded sum plus the edge field once
+// more: horizontally H_k += X_k for the fields of the image's first pixel
+// (eml: byte columns [0, CH), always pairs 0..CH-1 of one lane) and of its last
+// pixel (emr: byte columns [row_bytes - CH, row_bytes)); two masks, a row one
+// pixel wide takes both terms on the same byte.  Vertically the edge row is
+// copied into its out-of-image neighbour instead (edge_rows below, where the
+// zero border re-zeroes that row): inside a wave between two steps, and across
+// waves by reading the wave's OWN boundary row back from LDS (above_own: global
+// row 0 is this wave's first register row; below_own: the last image row is
+// its last) — no arithmetic in the step, so interior tiles pay nothing.  `h`
+// is tile-uniform, the two flags wave-uniform.  The zero border carries nothing.
+template <int CH, int NP, bool REP>
+struct EdgeFix {};
+template <int CH, int NP>
+struct EdgeFix<CH, NP, true> {
+  u32 eml[CH], emr[NP];
+  bool h;
+  bool above_own, below_own;
+};
+
+// Field masks of a lane whose pairs sit at byte columns pa + k (strip A, low
+// field) and pb + k (strip B, high field; pb < 0 and no strip B: pass hasB).
+template <int CH, int NP>
+__device__ __forceinline__ void edge_masks(EdgeFix<CH, NP, true>& e, int pa, int pb, bool hasB, int row_bytes) {
+#pragma unroll
+  for (int k = 0; k < CH; ++k) e.eml[k] = (pa == 0 ? 0xffffu : 0u) | (hasB && pb == 0 ? 0xffff0000u : 0u);
+#pragma unroll
+  for (int k = 0; k < NP; ++k) {
+    const int ca = pa + k, cb = pb + k;
+    e.emr[k] = (ca >= row_bytes - CH && ca < row_bytes && ca >= 0 ? 0xffffu : 0u) |
+               (hasB && cb >= row_bytes - CH && cb < row_bytes && cb >= 0 ? 0xffff0000u : 0u);
+  }
+}
+
+// horiz() under the launch's border rule.
+template <int CH, int NP, bool REP>
+__device__ __forceinline__ void horiz_b(const u32 (&X)[NP], u32 (&H)[NP], const EdgeFix<CH, NP, REP>& e) {
+  horiz<CH, NP>(X, H);
+  if constexpr (REP) {
+    if (e.h) {
+#pragma unroll
+      for (int k = 0; k < CH; ++k) H[k] += X[k] & e.eml[k];
+#pragma unroll
+      for (int k = 0; k < NP; ++k) H[k] += X[k] & e.emr[k];
+    }
+  }
+}
+
 template <int NP>
 struct Chunk;  // raw bytes of one lane's chunk in one strip
 template <>
@@ -134,6 +184,35 @@ __device__ __forceinline__ void store_bytes(uint8_t* p, const typename Chunk<NP>
   for (int k = 0; k < n; ++k) p[k] = static_cast<uint8_t>(w[k >> 2] >> (8 * (k & 3)));
 }
 
+// Replicate border, rows inside one wave: the register row just above global
+// row 0 takes row 0's values and the one just below the last image row takes
+// that row's (the other out-of-image rows stay zero; none is ever stored).
+// Runs after the load and after every step's re-zeroing, only in waves that
+// hold out-of-image rows — which are zero on entry, so the copy is an OR under
+// a wave-uniform mask: every row is updated in place, whichever row it is
+// (a store to "row out_top - 1" would index the register tile dynamically and
+// send it to scratch memory).
+template <int NP, int M>
+__device__ __forceinline__ void edge_rows(u32 (&D)[M][NP], int out_top, int out_bot) {
+  // Recompute the row masks here each time: hoisted out of the step loop, the
+  // 2 (M - 1) of them stay live in SGPRs through every step and spill.
+  out_top = __builtin_amdgcn_readfirstlane(out_top);  // wave-uniform by construction
+  out_bot = __builtin_amdgcn_readfirstlane(out_bot);
+  asm volatile("" : "+s"(out_top), "+s"(out_bot));
+#pragma unroll
+  for (int i = 0; i + 1 < M; ++i) {
+    const u32 take = i + 1 == out_top ? 0xffffffffu : 0u;
+#pragma unroll
+    for (int k = 0; k < NP; ++k) D[i][k] |= D[i + 1][k] & take;
+  }
+#pragma unroll
+  for (int i = M - 1; i >= 1; --i) {
+    const u32 take = i == out_bot ? 0xffffffffu : 0u;
+#pragma unroll
+    for (int k = 0; k < NP; ++k) D[i][k] |= D[i - 1][k] & take;
+  }
+}
+
 // One repetition of a wave's M register rows, interior first: the wave
 // publishes its two boundary rows to LDS, computes its interior rows 1..M-2
 // (they need only its own registers) while the other waves catch up, and only
@@ -142,7 +221,8 @@ __device__ __forceinline__ void store_bytes(uint8_t* p, const typename Chunk<NP>
 // rows of arithmetic (measured 2-13 % over exchanging first).  MODE picks the
 // truncation: 0 floor(S/16); 1 keeps 16 x floor(S/16) (one AND; the next step
 // then sums values < 2^12 into fields < 2^16); 2 floor(S/256) of such a step.
-// Out-of-image rows and columns are re-zeroed after every step.
+// Out-of-image rows and columns are re-zeroed after every step (under the
+// replicate border too: its corrections rely on those zeros, see EdgeFix).
 template <int MODE>
 __device__ __forceinline__ u32 trunc_sum(u32 S) {
   if constexpr (MODE == 0) return (S >> 4) & 0x00ff00ffu;
@@ -152,10 +232,10 @@ __device__ __forceinline__ u32 trunc_sum(u32 S) {
 
 // lds[parity][wave][2][quad][lane]: slot 0 = the wave's top row, slot 1 its
 // bottom row.
-template <int CH, int NP, int M, int NW, int MODE = 0>
+template <int CH, int NP, int M, int NW, int MODE = 0, bool REP = false>
 __device__ __forceinline__ void swar_step(u32 (&D)[M][NP], uint4 (&lds)[2][NW][2][NP / 4][64], int par, int w,
                                              int lane, bool needs_mask, const u32 (&cm)[NP], int out_top,
-                                             int out_bot) {
+                                             int out_bot, const EdgeFix<CH, NP, REP>& ef) {
   static_assert(M >= 2, "interior-first step needs two register rows per wave");
   constexpr int NQ = NP / 4;
 #pragma unroll
@@ -168,8 +248,8 @@ __device__ __forceinline__ void swar_step(u32 (&D)[M][NP], uint4 (&lds)[2][NW][2
   // S_{i-1} + S_i: two v_add_u32 per pair (keep(): no v_add3_u32 that would
   // redo an add the next row needs anyway).
   u32 H0[NP], Hc[NP], S01[NP], Sc[NP];
-  horiz<CH, NP>(D[0], H0);
-  horiz<CH, NP>(D[1], Hc);
+  horiz_b<CH, NP, REP>(D[0], H0, ef);
+  horiz_b<CH, NP, REP>(D[1], Hc, ef);
 #pragma unroll
   for (int k = 0; k < NP; ++k) {
     S01[k] = keep(H0[k] + Hc[k]);
@@ -178,7 +258,7 @@ __device__ __forceinline__ void swar_step(u32 (&D)[M][NP], uint4 (&lds)[2][NW][2
 #pragma unroll
   for (int i = 1; i + 1 < M; ++i) {
     u32 Hn[NP];
-    horiz<CH, NP>(D[i + 1], Hn);
+    horiz_b<CH, NP, REP>(D[i + 1], Hn, ef);
 #pragma unroll
     for (int k = 0; k < NP; ++k) {
       const u32 Sn = keep(Hc[k] + Hn[k]);
@@ -190,18 +270,31 @@ __device__ __forceinline__ void swar_step(u32 (&D)[M][NP], uint4 (&lds)[2][NW][2
   // Sc = S_{M-2} = H[M-2] + H[M-1], Hc = H[M-1] (old rows); S01 = H[0] + H[1].
   __syncthreads();
   {
-    const int wa = w > 0 ? w - 1 : 0;       // wave 0: tile top halo, value irrelevant
-    const int wb = w < NW - 1 ? w + 1 : w;  // last wave: tile bottom halo
+    int wa = w > 0 ? w - 1 : 0;       // wave 0: tile top halo, value irrelevant
+    int wb = w < NW - 1 ? w + 1 : w;  // last wave: tile bottom halo
+    int sa = 1, sb = 0;               // the upper wave's bottom row, the lower wave's top row
+    if constexpr (REP) {
+      // the row above global row 0 is row 0, the row below the last is the
+      // last: this wave's own published boundary row
+      if (ef.above_own) {
+        wa = w;
+        sa = 0;
+      }
+      if (ef.below_own) {
+        wb = w;
+        sb = 1;
+      }
+    }
     u32 A[NP], B[NP];
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
-      const uint4 av = lds[par][wa][1][q][lane], bv = lds[par][wb][0][q][lane];
+      const uint4 av = lds[par][wa][sa][q][lane], bv = lds[par][wb][sb][q][lane];
       A[4 * q] = av.x; A[4 * q + 1] = av.y; A[4 * q + 2] = av.z; A[4 * q + 3] = av.w;
       B[4 * q] = bv.x; B[4 * q + 1] = bv.y; B[4 * q + 2] = bv.z; B[4 * q + 3] = bv.w;
     }
     u32 Ha[NP], Hb[NP];
-    horiz<CH, NP>(A, Ha);
-    horiz<CH, NP>(B, Hb);
+    horiz_b<CH, NP, REP>(A, Ha, ef);
+    horiz_b<CH, NP, REP>(B, Hb, ef);
 #pragma unroll
     for (int k = 0; k < NP; ++k) {
       D[0][k] = trunc_sum<MODE>(keep(Ha[k] + H0[k]) + S01[k]);
@@ -220,6 +313,7 @@ __device__ __forceinline__ void swar_step(u32 (&D)[M][NP], uint4 (&lds)[2][NW][2
       if (i < out_top || i >= out_bot)
 #pragma unroll
         for (int k = 0; k < NP; ++k) D[i][k] = 0;
+    if constexpr (REP) edge_rows<NP, M>(D, out_top, out_bot);
   }
 }
 

@@ -59,6 +59,7 @@ EngineOptions engine_options(const CliConfig& c, const ImageGeom& g, int world, 
   EngineOptions o;
   o.device = device;
   o.variant = c.variant;
+  o.border = c.border;
   o.overlap = c.overlap;
   o.use_graph = c.graph && world == 1;
   const bool fusable = supports_fusion(f, c.variant);
@@ -81,7 +82,8 @@ EngineOptions engine_options(const CliConfig& c, const ImageGeom& g, int world, 
 int64_t compare_with_oracle(const CliConfig& c, const ImageGeom& g, const uint8_t* result) {
   std::vector<uint8_t> in(static_cast<size_t>(g.bytes())), ref(static_cast<size_t>(g.bytes()));
   load_rows(c, g, 0, g.height, in.data(), g.row_bytes());
-  cpu_convolve(Filter::by_name(c.filter), g, in.data(), ref.data(), c.reps, CpuBackend::OpenMP, c.threads);
+  cpu_convolve(Filter::by_name(c.filter), g, in.data(), ref.data(), c.reps, CpuBackend::OpenMP, c.threads,
+               c.border);
   int64_t bad = 0;
   for (size_t i = 0; i < ref.size(); ++i) bad += ref[i] != result[i];
   return bad;
@@ -120,7 +122,7 @@ AppReport run_cpu(const CliConfig& c) {
   };
   const double l0 = wall_seconds();
   for (int done = 0; done < c.reps;) {
-    cpu_step(f, g.channels, lay, src, dst, 0, g.height, be);
+    cpu_step(f, g.channels, lay, src, dst, 0, g.height, be, c.border, 0, g.height);
     std::swap(src, dst);  // newest result is always `src`
     ++done;
     if (c.checkpoint_every > 0 && done % c.checkpoint_every == 0 && done < c.reps) {
@@ -175,10 +177,10 @@ double seconds_since_exec() {
 }  // namespace
 
 // Resources a resident server keeps between jobs (service.hpp): engines per
-// (geometry, filter, launch options), least recently used first out, and one
+// (geometry, filter, launch options, border), least recently used first out, and one
 // pinned staging buffer grown on demand.
 struct JobCache {
-  using Key = std::tuple<int64_t, int64_t, int, std::string, int, int, int, bool, bool, bool>;
+  using Key = std::tuple<int64_t, int64_t, int, std::string, int, int, int, bool, bool, bool, int>;
   std::list<std::pair<Key, std::unique_ptr<BandEngine>>> engines;
   PinnedBuffer host;
   int max_engines = 8;
@@ -187,7 +189,8 @@ struct JobCache {
   BandEngine& engine(const ImageGeom& g, const Filter& f, const EngineOptions& o, const std::string& fname,
                      bool* fresh) {
     const Key k{g.width, g.height, channel_count(g.channels), fname, o.fuse, o.halo_depth,
-                static_cast<int>(o.variant), o.overlap, o.use_graph, o.kernel_copies};
+                static_cast<int>(o.variant), o.overlap, o.use_graph, o.kernel_copies,
+                static_cast<int>(o.border)};  // an engine applies ONE border rule to every launch
     for (auto it = engines.begin(); it != engines.end(); ++it)
       if (it->first == k) {
         engines.splice(engines.begin(), engines, it);
@@ -440,7 +443,7 @@ AppReport run_auto(const CliConfig& c) {
     double best = 1e30, spent = 0;
     for (int t = 0; t < 3 && spent < 3e-3; ++t) {
       const double s0 = wall_seconds();
-      cpu_step(f, g.channels, sl, sa.data(), sb.data(), 0, sample, CpuBackend::OpenMP);
+      cpu_step(f, g.channels, sl, sa.data(), sb.data(), 0, sample, CpuBackend::OpenMP, c.border, 0, sample);
       const double dt = wall_seconds() - s0;
       best = std::min(best, dt);
       spent += dt;
@@ -486,7 +489,7 @@ AppReport run_auto(const CliConfig& c) {
   uint8_t* dst = fb.data();
   int done = 0;
   auto cpu_rep = [&] {
-    cpu_step(f, g.channels, lay, src, dst, 0, g.height, CpuBackend::OpenMP);
+    cpu_step(f, g.channels, lay, src, dst, 0, g.height, CpuBackend::OpenMP, c.border, 0, g.height);
     std::swap(src, dst);  // newest result is always `src`
     ++done;
   };
@@ -1003,7 +1006,8 @@ std::string run_bench_impl(const CliConfig& c) {
     const Band b = row_band(g.height, c.emulate_world, c.emulate_rank);
     std::vector<uint8_t> in(static_cast<size_t>(g.bytes())), ref(static_cast<size_t>(g.bytes()));
     load_rows(c, g, 0, g.height, in.data(), g.row_bytes());
-    cpu_convolve(Filter::by_name(c.filter), g, in.data(), ref.data(), c.reps, CpuBackend::OpenMP, c.threads);
+    cpu_convolve(Filter::by_name(c.filter), g, in.data(), ref.data(), c.reps, CpuBackend::OpenMP, c.threads,
+               c.border);
     mism = 0;
     for (int64_t i = b.y0 * g.row_bytes(); i < (b.y0 + b.rows) * g.row_bytes(); ++i) mism += ref[i] != image[i];
   } else if (c.check) {
@@ -1034,7 +1038,7 @@ std::string run_bench_impl(const CliConfig& c) {
      << ", \"stream_chunks\": " << c.stream_chunks
      << ", \"cu_mask_queues\": " << (c.cu_mask_queues ? "true" : "false")
      << ", \"head_on_slot_streams\": " << (c.head_on_slot_streams ? "true" : "false")
-     << ", \"numa_bind\": " << (c.numa_bind ? "true" : "false") << ", \"halo_depth\": " << sh->halo << ", \"fuse\": " << sh->fuse
+     << ", \"border\": \"" << border_name(c.border) << "\", \"numa_bind\": " << (c.numa_bind ? "true" : "false") << ", \"halo_depth\": " << sh->halo << ", \"fuse\": " << sh->fuse
      << ", \"launches_per_step\": " << sh->launches << "}, \"latency_ms\": " << lat
      << ", \"copy_floor\": {\"pair_ms\": " << pair << "}";
   if (mism >= 0)
@@ -1083,7 +1087,7 @@ std::string report_json(const CliConfig& c, const AppReport& r) {
   const double px = static_cast<double>(c.width) * static_cast<double>(c.height) * c.reps;
   os << "{\"width\": " << c.width << ", \"height\": " << c.height << ", \"channels\": \""
      << channels_name(c.channels) << "\", \"reps\": " << c.reps << ", \"filter\": \"" << c.filter
-     << "\", \"backend\": \""
+     << "\", \"border\": \"" << border_name(c.border) << "\", \"backend\": \""
      << (c.backend == Backend::Hip ? "hip" : c.backend == Backend::Omp ? "omp" : c.backend == Backend::Auto ? "auto" : "cpu")
      << "\", \"gpus\": " << r.gpus << ", \"kernel\": \"" << r.kernel << "\", \"halo\": " << r.halo
      << ", \"fuse\": " << r.fuse << ", \"launches\": " << r.launches << ", \"exchanges\": " << r.exchanges

@@ -38,6 +38,8 @@ std::string help_text(const std::string& prog) {
          "  --auto-gpu-min S          --backend auto: CPU seconds above which the GPU runs the job (default 0.1)\n"
          "  --gpus N                  row-band decomposition over N GPUs, one process each (RCCL halos)\n"
          "  --filter {gaussian,box,edge}  3x3 filter (default gaussian)\n"
+         "  --border {zero,replicate} what a tap reads outside the image: zeros (default, the reference's\n"
+         "                            rule) or the nearest image pixel (no dark frame after many repetitions)\n"
          "  --halo D                  ghost rows exchanged at once (default: auto)\n"
          "  --fuse T                  repetitions fused per kernel launch (default: auto)\n"
          "  --no-overlap              do not overlap halo exchange with interior compute\n"
@@ -116,6 +118,10 @@ CliConfig parse_cli(const std::vector<std::string>& args) {
       c.filter = next("--filter");
       if (c.filter != "gaussian" && c.filter != "box" && c.filter != "edge")
         PCONV_FAIL("invalid --filter '" + c.filter + "' (gaussian|box|edge)");
+    } else if (a == "--border") {
+      const std::string v = next("--border");
+      if (v != "zero" && v != "replicate") PCONV_FAIL("invalid --border '" + v + "' (zero|replicate)");
+      c.border = parse_border(v);
     } else if (a == "--halo") {
       c.halo = static_cast<int>(parse_int(next("--halo"), "--halo", 1, 1 << 20));
     } else if (a == "--fuse") {

@@ -66,6 +66,14 @@ Channels parse_channels(const std::string& s) {
   PCONV_FAIL("unknown image type '" + s + "' (expected grey|rgb|rgba)");
 }
 
+const char* border_name(Border b) { return b == Border::Replicate ? "replicate" : "zero"; }
+
+Border parse_border(const std::string& s) {
+  if (s == "zero") return Border::Zero;
+  if (s == "replicate") return Border::Replicate;
+  PCONV_FAIL("unknown border '" + s + "' (expected zero|replicate)");
+}
+
 // ---------------------------------------------------------------- filters
 Filter Filter::custom(const std::array<int, 9>& taps, int divisor, const std::string& name) {
   PCONV_CHECK(divisor > 0, "filter divisor must be positive");

@@ -133,15 +133,42 @@ void row_float(const Filter& f, const uint8_t* a, const uint8_t* b, const uint8_
     row_float_base<CH>(f.weights.data(), a, b, c, o, n);
 }
 
+// Replicate border: row `p` (n bytes) with its first and last pixel repeated
+// once on either side, in `buf` (n + 2 CH bytes); returns the column-0 pointer.
+// The source frame is only read: its pad columns and ghost rows stay as they are.
+template <int CH>
+const uint8_t* edge_padded(const uint8_t* p, int64_t n, uint8_t* buf) {
+  std::memcpy(buf + CH, p, static_cast<size_t>(n));
+  for (int k = 0; k < CH; ++k) {
+    buf[k] = p[k];
+    buf[CH + n + k] = p[n - CH + k];
+  }
+  return buf + CH;
+}
+
 template <int CH>
 void step_rows(const Filter& f, const FrameLayout& lay, const uint8_t* src, uint8_t* dst, int64_t r0, int64_t r1,
-               CpuBackend be) {
+               CpuBackend be, Border border, int64_t g_row0, int64_t height) {
   const int64_t n = lay.row_bytes;
   auto body = [&](int64_t r) {
     const uint8_t* a = src + lay.offset(r - 1);
     const uint8_t* b = src + lay.offset(r);
     const uint8_t* c = src + lay.offset(r + 1);
     uint8_t* o = dst + lay.offset(r);
+    if (border == Border::Replicate) {
+      // Taps clamp to the GLOBAL image: the row above global row 0 is row 0,
+      // the row below the last is the last; columns through padded copies, so
+      // the same row kernels (integer / float, baseline / AVX2) serve.
+      thread_local std::vector<uint8_t> rows3;
+      const size_t w = static_cast<size_t>(n + 2 * CH);
+      if (rows3.size() < 3 * w) rows3.resize(3 * w);
+      const int64_t g = g_row0 + r;
+      const uint8_t* pa = g - 1 >= 0 ? a : b;
+      const uint8_t* pc = g + 1 < height ? c : b;
+      a = edge_padded<CH>(pa, n, rows3.data());
+      c = edge_padded<CH>(pc, n, rows3.data() + 2 * w);
+      b = edge_padded<CH>(b, n, rows3.data() + w);
+    }
     if (f.binomial121)
       row_binomial<CH>(a, b, c, o, n);
     else if (f.int_exact)
@@ -164,25 +191,29 @@ void step_rows(const Filter& f, const FrameLayout& lay, const uint8_t* src, uint
 }  // namespace
 
 void cpu_step(const Filter& f, Channels ch, const FrameLayout& lay, const uint8_t* src_frame, uint8_t* dst_frame,
-              int64_t r0, int64_t r1, CpuBackend be) {
+              int64_t r0, int64_t r1, CpuBackend be, Border border, int64_t g_row0, int64_t height) {
   PCONV_CHECK(r0 >= -lay.halo + 1 && r1 <= lay.rows + lay.halo - 1 && r0 <= r1, "cpu_step: rows out of frame");
+  if (height < 0) height = g_row0 + lay.rows;  // the frame's owned rows end the image
+  if (border != Border::Zero)
+    PCONV_CHECK(r0 >= r1 || (g_row0 + r0 >= 0 && g_row0 + r1 <= height),
+                "cpu_step: a non-zero border computes rows of the global image only");
   switch (ch) {
-    case Channels::Grey: step_rows<1>(f, lay, src_frame, dst_frame, r0, r1, be); break;
-    case Channels::Rgb: step_rows<3>(f, lay, src_frame, dst_frame, r0, r1, be); break;
-    case Channels::Rgba: step_rows<4>(f, lay, src_frame, dst_frame, r0, r1, be); break;
+    case Channels::Grey: step_rows<1>(f, lay, src_frame, dst_frame, r0, r1, be, border, g_row0, height); break;
+    case Channels::Rgb: step_rows<3>(f, lay, src_frame, dst_frame, r0, r1, be, border, g_row0, height); break;
+    case Channels::Rgba: step_rows<4>(f, lay, src_frame, dst_frame, r0, r1, be, border, g_row0, height); break;
   }
 }
 
 void cpu_fused_launch(const Filter& f, Channels ch, const FrameLayout& lay, const uint8_t* src_frame,
                       uint8_t* dst_frame, int64_t lo, int64_t hi, int steps, int64_t g_row0, int64_t height,
-                      CpuBackend be) {
+                      CpuBackend be, Border border) {
   PCONV_CHECK(steps >= 1 && lo <= hi, "cpu_fused_launch: bad arguments");
   PCONV_CHECK(lo - steps >= -lay.halo && hi + steps <= lay.rows + lay.halo, "cpu_fused_launch: rows exceed frame");
   if (lo == hi) return;
   if (steps == 1) {
     // Single step never writes rows outside the image: clip like the kernels' caller.
     const int64_t a = std::max(lo, -g_row0), b = std::min(hi, height - g_row0);
-    if (a < b) cpu_step(f, ch, lay, src_frame, dst_frame, a, b, be);
+    if (a < b) cpu_step(f, ch, lay, src_frame, dst_frame, a, b, be, border, g_row0, height);
     return;
   }
   const size_t n = static_cast<size_t>(lay.bytes());
@@ -192,7 +223,7 @@ void cpu_fused_launch(const Filter& f, Channels ch, const FrameLayout& lay, cons
   for (int j = 1; j <= steps; ++j) {
     const int64_t ext = steps - j;
     const int64_t a = std::max(lo - ext, -g_row0), b = std::min(hi + ext, height - g_row0);
-    if (a < b) cpu_step(f, ch, lay, cur, nxt, a, b, be);
+    if (a < b) cpu_step(f, ch, lay, cur, nxt, a, b, be, border, g_row0, height);
     std::swap(cur, nxt);
   }
   for (int64_t r = lo; r < hi; ++r) {
@@ -251,7 +282,7 @@ int configure_cpu_threads(int share) {
 }
 
 void cpu_convolve(const Filter& f, const ImageGeom& geom, const uint8_t* in, uint8_t* out, int reps, CpuBackend be,
-                  int threads) {
+                  int threads, Border border) {
   geom.validate();
   PCONV_CHECK(reps >= 0, "repetitions must be >= 0");
   const int64_t rb = geom.row_bytes();
@@ -264,7 +295,7 @@ void cpu_convolve(const Filter& f, const ImageGeom& geom, const uint8_t* in, uin
   uint8_t* src = fa.data();
   uint8_t* dst = fb.data();
   for (int t = 0; t < reps; ++t) {
-    cpu_step(f, geom.channels, lay, src, dst, 0, geom.height, be);
+    cpu_step(f, geom.channels, lay, src, dst, 0, geom.height, be, border, 0, geom.height);
     std::swap(src, dst);  // newest result is always in `src` (fixes SURVEY §A3)
   }
   if (be == CpuBackend::OpenMP && threads > 0) omp_set_num_threads(saved);

@@ -30,6 +30,10 @@ BandEngine::BandEngine(const ImageGeom& geom, const Band& band, const Filter& fi
     : geom_(geom), band_(band), filter_(filter), opt_(opt) {
   geom_.validate();
   PCONV_CHECK(band.rows >= 1 && band.y0 >= 0 && band.y0 + band.rows <= geom.height, "band outside image");
+  PCONV_CHECK(opt.border == Border::Zero || opt.variant == KernelVariant::Auto ||
+                  opt.variant == KernelVariant::Temporal || opt.variant == KernelVariant::FloatTemporal,
+              "border '" + std::string(border_name(opt.border)) + "' not supported by kernel '" +
+                  std::string(kernel_variant_name(opt.variant)) + "' (temporal and float_temporal only)");
   const PlanConfig c = engine_plan_config(geom_, band_, filter_, opt_);
   opt_.fuse = c.fuse;
   opt_.halo_depth = c.halo_depth;
@@ -185,6 +189,7 @@ StencilLaunch BandEngine::make_launch(const LaunchSpec& l, int cur) const {
   a.steps = l.steps;
   a.g_row0 = band_.y0;
   a.height = geom_.height;
+  a.border = opt_.border;
   return a;
 }
 

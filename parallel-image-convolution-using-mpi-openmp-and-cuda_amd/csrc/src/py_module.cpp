@@ -189,16 +189,17 @@ PYBIND11_MODULE(_pconv_native, m) {
   m.def(
       "cpu_convolve",
       [](py::buffer in, py::buffer out, int64_t w, int64_t h, const std::string& ch, int reps, py::object filter,
-         bool omp, int threads) {
+         bool omp, int threads, const std::string& border) {
         const ImageGeom g = make_geom(w, h, ch);
+        const Border bd = parse_border(border);
         const HostView a = host_view(in, false), b = host_view(out, true);
         PCONV_CHECK(a.size == g.bytes() && b.size == g.bytes(), "buffer size does not match the image geometry");
         const Filter f = make_filter(filter);
         py::gil_scoped_release nogil;
-        cpu_convolve(f, g, a.ptr, b.ptr, reps, omp ? CpuBackend::OpenMP : CpuBackend::Serial, threads);
+        cpu_convolve(f, g, a.ptr, b.ptr, reps, omp ? CpuBackend::OpenMP : CpuBackend::Serial, threads, bd);
       },
       py::arg("src"), py::arg("dst"), py::arg("width"), py::arg("height"), py::arg("channels"), py::arg("reps"),
-      py::arg("filter") = "gaussian", py::arg("omp") = false, py::arg("threads") = 0);
+      py::arg("filter") = "gaussian", py::arg("omp") = false, py::arg("threads") = 0, py::arg("border") = "zero");
   m.def("default_cpu_threads", &default_cpu_threads,
         "OpenMP team size used when none is set: affinity CPUs capped by the cgroup quota, minus one");
   m.def(
@@ -214,18 +215,22 @@ PYBIND11_MODULE(_pconv_native, m) {
   m.def(
       "cpu_fused_launch",
       [](py::object filter, const std::string& ch, int64_t row_bytes, int64_t rows, int64_t halo, py::buffer src,
-         py::buffer dst, int64_t lo, int64_t hi, int steps, int64_t g_row0, int64_t height, bool omp) {
+         py::buffer dst, int64_t lo, int64_t hi, int steps, int64_t g_row0, int64_t height, bool omp,
+         const std::string& border) {
+        const Border bd = parse_border(border);
         const FrameLayout lay = FrameLayout::make(row_bytes, rows, halo);
         const HostView a = host_view(src, false), b = host_view(dst, true);
         PCONV_CHECK(a.size == lay.bytes() && b.size == lay.bytes(), "frame buffer size mismatch");
         const Filter f = make_filter(filter);
         py::gil_scoped_release nogil;
         cpu_fused_launch(f, parse_channels(ch), lay, a.ptr, b.ptr, lo, hi, steps, g_row0, height,
-                         omp ? CpuBackend::OpenMP : CpuBackend::Serial);
+                         omp ? CpuBackend::OpenMP : CpuBackend::Serial, bd);
       },
       py::arg("filter"), py::arg("channels"), py::arg("row_bytes"), py::arg("rows"), py::arg("halo"), py::arg("src"),
       py::arg("dst"), py::arg("lo"), py::arg("hi"), py::arg("steps"), py::arg("g_row0"), py::arg("height"),
-      py::arg("omp") = false);
+      py::arg("omp") = false, py::arg("border") = "zero");
+  m.def("border_names", []() { return std::vector<std::string>{border_name(Border::Zero), border_name(Border::Replicate)}; },
+        "border modes every backend takes (the first is the default and the reference's)");
 
   // ---------------------------------------------------------------- raw I/O
   m.def("output_path_for", &output_path_for, py::arg("path"), py::arg("prefix") = "blur_");
@@ -352,8 +357,9 @@ PYBIND11_MODULE(_pconv_native, m) {
       "launch_stencil",
       [](py::object filter, const std::string& ch, uintptr_t src, uintptr_t dst, int64_t pitch, int64_t row_bytes,
          int64_t r0, int64_t r1, int64_t frame_lo, int64_t frame_hi, int steps, int64_t g_row0, int64_t height,
-         uintptr_t stream, const std::string& variant) {
+         uintptr_t stream, const std::string& variant, const std::string& border) {
         StencilLaunch a;
+        a.border = parse_border(border);
         a.src = reinterpret_cast<const uint8_t*>(src);
         a.dst = reinterpret_cast<uint8_t*>(dst);
         a.pitch = pitch;
@@ -371,7 +377,7 @@ PYBIND11_MODULE(_pconv_native, m) {
       py::arg("filter"), py::arg("channels"), py::arg("src"), py::arg("dst"), py::arg("pitch"), py::arg("row_bytes"),
       py::arg("r0"), py::arg("r1"), py::arg("frame_lo"), py::arg("frame_hi"), py::arg("steps") = 1,
       py::arg("g_row0") = 0, py::arg("height") = (int64_t(1) << 40), py::arg("stream") = 0,
-      py::arg("variant") = "auto");
+      py::arg("variant") = "auto", py::arg("border") = "zero");
   m.def("set_swar_shape", &set_swar_shape, py::arg("lw") = 0, py::arg("m") = 0, py::arg("nw") = 0,
         "Force the SWAR temporal tile shape (lw=0: back to the latency model).");
   m.def("swar_shapes", []() {
@@ -466,8 +472,9 @@ PYBIND11_MODULE(_pconv_native, m) {
   py::class_<BandEngine>(m, "BandEngine")
       .def(py::init([](int64_t w, int64_t h, const std::string& ch, py::object filter, int rank, int world,
                        int device, int halo, int fuse, bool overlap, bool graph, const std::string& variant,
-                       bool kernel_copies, int stream_chunks) {
+                       bool kernel_copies, int stream_chunks, const std::string& border) {
              EngineOptions o;
+             o.border = parse_border(border);
              o.stream_chunks = stream_chunks;
              o.kernel_copies = kernel_copies;
              o.device = device;
@@ -482,7 +489,8 @@ PYBIND11_MODULE(_pconv_native, m) {
            py::arg("width"), py::arg("height"), py::arg("channels"), py::arg("filter") = "gaussian",
            py::arg("rank") = 0, py::arg("world") = 1, py::arg("device") = 0, py::arg("halo") = 1, py::arg("fuse") = 1,
            py::arg("overlap") = true, py::arg("graph") = false, py::arg("variant") = "auto",
-           py::arg("kernel_copies") = false, py::arg("stream_chunks") = 0)
+           py::arg("kernel_copies") = false, py::arg("stream_chunks") = 0, py::arg("border") = "zero")
+      .def_property_readonly("border", [](const BandEngine& e) { return std::string(border_name(e.options().border)); })
       .def_property_readonly("band", &BandEngine::band)
       .def("stream_plan", &BandEngine::stream_plan, py::arg("reps"), py::arg("in_r0"), py::arg("in_r1"))
       .def_property_readonly("halo", [](const BandEngine& e) { return e.layout().halo; })
@@ -580,10 +588,12 @@ PYBIND11_MODULE(_pconv_native, m) {
       .def_static(
           "for_band",
           [](int64_t w, int64_t h, const std::string& ch, py::object filter, const Band& band, int device, int halo,
-             int fuse, bool overlap, const std::string& variant, bool graph, bool capture_exchanges) {
+             int fuse, bool overlap, const std::string& variant, bool graph, bool capture_exchanges,
+             const std::string& border) {
             // An explicit band (tests: e.g. a single rank whose up/down
             // neighbour is itself, to drive RCCL send/recv-to-self).
             EngineOptions o;
+            o.border = parse_border(border);
             o.device = device;
             o.halo_depth = halo;
             o.fuse = fuse;
@@ -595,7 +605,8 @@ PYBIND11_MODULE(_pconv_native, m) {
           },
           py::arg("width"), py::arg("height"), py::arg("channels"), py::arg("filter"), py::arg("band"),
           py::arg("device") = 0, py::arg("halo") = 1, py::arg("fuse") = 1, py::arg("overlap") = true,
-          py::arg("variant") = "auto", py::arg("graph") = false, py::arg("capture_exchanges") = false)
+          py::arg("variant") = "auto", py::arg("graph") = false, py::arg("capture_exchanges") = false,
+          py::arg("border") = "zero")
       .def("set_stream_trace", &BandEngine::set_stream_trace, py::arg("on"),
            "diagnostics: time the next streamed images chunk by chunk (stream_trace())")
       .def("stream_trace", &BandEngine::stream_trace, py::call_guard<py::gil_scoped_release>(),
@@ -615,8 +626,9 @@ PYBIND11_MODULE(_pconv_native, m) {
                        int concurrent, bool graphs, bool step_graphs, py::object band, bool slot_comm,
                        int stream_chunks, bool cu_mask_queues, bool head_on_slot_streams,
                        int64_t stream_min_bytes, bool head_alt_uploads, std::vector<int> stream_weights,
-                       bool lazy_head) {
+                       bool lazy_head, const std::string& border) {
              EngineOptions o;
+             o.border = parse_border(border);
              o.lazy_head = lazy_head;
              o.head_alt_uploads = head_alt_uploads;
              o.stream_chunks = stream_chunks;
@@ -644,7 +656,8 @@ PYBIND11_MODULE(_pconv_native, m) {
            py::arg("band") = py::none(), py::arg("slot_comm") = false, py::arg("stream_chunks") = 0,
            py::arg("cu_mask_queues") = true, py::arg("head_on_slot_streams") = true,
            py::arg("stream_min_bytes") = EngineOptions{}.stream_min_bytes, py::arg("head_alt_uploads") = true,
-           py::arg("stream_weights") = std::vector<int>{}, py::arg("lazy_head") = EngineOptions{}.lazy_head)
+           py::arg("stream_weights") = std::vector<int>{}, py::arg("lazy_head") = EngineOptions{}.lazy_head,
+           py::arg("border") = "zero")
       .def_property_readonly("slots", &BandPipeline::slots)
       .def("slot", &BandPipeline::slot, py::return_value_policy::reference_internal)
       .def("attach_rccl",
@@ -700,8 +713,9 @@ PYBIND11_MODULE(_pconv_native, m) {
 
   py::class_<LocalCluster>(m, "LocalCluster")
       .def(py::init([](int64_t w, int64_t h, const std::string& ch, py::object filter, int bands, int device, int halo,
-                       int fuse, const std::string& variant, bool overlap) {
+                       int fuse, const std::string& variant, bool overlap, const std::string& border) {
              EngineOptions o;
+             o.border = parse_border(border);
              o.device = device;
              o.halo_depth = halo;
              o.fuse = fuse;
@@ -711,7 +725,7 @@ PYBIND11_MODULE(_pconv_native, m) {
            }),
            py::arg("width"), py::arg("height"), py::arg("channels"), py::arg("filter") = "gaussian",
            py::arg("bands") = 2, py::arg("device") = 0, py::arg("halo") = 1, py::arg("fuse") = 1,
-           py::arg("variant") = "auto", py::arg("overlap") = true)
+           py::arg("variant") = "auto", py::arg("overlap") = true, py::arg("border") = "zero")
       .def("upload",
            [](LocalCluster& c, py::buffer host, bool preload_halo) {
              c.upload(host_view(host, false).ptr, preload_halo);

@@ -50,21 +50,22 @@ class FilterPipeline:
     def __repr__(self) -> str:
         return "FilterPipeline(" + ",".join(f"{s.filter.name}:{s.reps}" for s in self.stages) + ")"
 
-    def apply(self, image, backend: str = "auto", device: Optional[int] = None):
-        """Run every stage in order; returns the same container type as ``image``."""
+    def apply(self, image, backend: str = "auto", device: Optional[int] = None, border: str = "zero"):
+        """Run every stage in order (each under the same ``border`` rule); returns
+        the same container type as ``image``."""
         from ..ops.stencil import convolve
 
         out = image
         for s in self.stages:
             if s.reps:
-                out = convolve(out, s.reps, s.filter, backend=backend, device=device)
+                out = convolve(out, s.reps, s.filter, backend=backend, device=device, border=border)
         return out
 
-    def reference(self, image):
+    def reference(self, image, border: str = "zero"):
         """Independent NumPy oracle of the whole pipeline."""
         from ..ops.reference import numpy_convolve
 
         out = image
         for s in self.stages:
-            out = numpy_convolve(out, s.reps, s.filter)
+            out = numpy_convolve(out, s.reps, s.filter, border)
         return out

@@ -5,7 +5,8 @@ so the two check each other (SURVEY §4 "keeps the C++ oracle honest").
 
 Semantics (reference ``mpi/mpi_convolution.c:301-322``): per
 channel, ``out[y][x] = trunc(sum_{k,l} w[k][l] * in[y+k-1][x+l-1])`` with zero
-padding, float32 multiply-then-add in row-major tap order starting from 0.0f.
+padding (``border="zero"``, the reference's rule) or with the indices clamped
+to the image (``border="replicate"``, ``np.pad(mode="edge")``), float32 multiply-then-add in row-major tap order starting from 0.0f.
 NumPy's float32 elementwise ops round each multiply and add separately (no FMA),
 which reproduces the reference bit for bit; integer-exact filters use
 ``(sum tap*p) >> shift`` directly.
@@ -16,6 +17,14 @@ import numpy as np
 
 from ..models.filters import get_filter
 
+BORDERS = ("zero", "replicate")
+
+
+def check_border(border: str) -> str:
+    if border not in BORDERS:
+        raise ValueError(f"unknown border {border!r} (expected zero|replicate)")
+    return border
+
 
 def _as_hwc(img: np.ndarray) -> np.ndarray:
     if img.ndim == 2:
@@ -25,11 +34,11 @@ def _as_hwc(img: np.ndarray) -> np.ndarray:
     raise ValueError("image must be (H, W) or (H, W, C)")
 
 
-def numpy_step(img: np.ndarray, filt="gaussian") -> np.ndarray:
+def numpy_step(img: np.ndarray, filt="gaussian", border: str = "zero") -> np.ndarray:
     f = get_filter(filt)
     x = _as_hwc(np.asarray(img, dtype=np.uint8))
     h, w, _ = x.shape
-    p = np.pad(x, ((1, 1), (1, 1), (0, 0)))
+    p = np.pad(x, ((1, 1), (1, 1), (0, 0)), mode="edge" if check_border(border) == "replicate" else "constant")
     if f.int_exact:
         acc = np.zeros(x.shape, dtype=np.int64)
         for k in range(3):
@@ -50,8 +59,9 @@ def numpy_step(img: np.ndarray, filt="gaussian") -> np.ndarray:
     return out.reshape(img.shape)
 
 
-def numpy_convolve(img: np.ndarray, reps: int = 1, filt="gaussian") -> np.ndarray:
+def numpy_convolve(img: np.ndarray, reps: int = 1, filt="gaussian", border: str = "zero") -> np.ndarray:
+    check_border(border)
     out = np.asarray(img, dtype=np.uint8).copy()
     for _ in range(int(reps)):
-        out = numpy_step(out, filt)
+        out = numpy_step(out, filt, border)
     return out

@@ -1,7 +1,8 @@
 """Stencil operators: the user-facing ``convolve`` and the persistent ``Engine``.
 
 ``convolve`` is the library form of the reference programs (repeated 3x3
-convolution of an 8-bit grey/RGB image, zero padded): it dispatches to
+convolution of an 8-bit grey/RGB image, zero padded — or, with
+``border="replicate"``, with the image's edge pixels repeated): it dispatches to
 
 * ``hip``   — the native CDNA4 kernels through a cached single-GPU
   :class:`Engine` (device-resident ping-pong frames, ``cuda/cuda_convolution.cu``
@@ -23,7 +24,7 @@ import torch
 
 from .._native import require_native
 from ..models.filters import get_filter
-from .reference import numpy_convolve
+from .reference import check_border, numpy_convolve
 
 _CHANNELS = {1: "grey", 3: "rgb", 4: "rgba"}
 
@@ -45,8 +46,9 @@ class Engine:
     """
 
     def __init__(self, width: int, height: int, channels: str = "grey", filter="gaussian", device: int = 0,
-                 fuse: Optional[int] = None, graph: bool = False, variant: str = "auto"):
+                 fuse: Optional[int] = None, graph: bool = False, variant: str = "auto", border: str = "zero"):
         n = require_native()
+        self.border = check_border(border)
         self.filter = get_filter(filter)
         nf = self.filter.to_native()
         if fuse is None:
@@ -55,7 +57,8 @@ class Engine:
         self.width, self.height, self.channels = int(width), int(height), channels
         self.device = int(device)
         self._eng = n.BandEngine(self.width, self.height, channels, nf, 0, 1, self.device, halo=int(fuse),
-                                 fuse=int(fuse), overlap=True, graph=bool(graph), variant=variant)
+                                 fuse=int(fuse), overlap=True, graph=bool(graph), variant=variant,
+                                 border=self.border)
         self.row_bytes = self._eng.row_bytes
 
     @property
@@ -102,11 +105,11 @@ _ENGINES: "OrderedDict[tuple, Engine]" = OrderedDict()
 _MAX_CACHED = 8
 
 
-def _cached_engine(w, h, ch, flt, device, fuse, graph, variant) -> Engine:
-    key = (w, h, ch, flt.taps, flt.divisor, device, fuse, graph, variant)
+def _cached_engine(w, h, ch, flt, device, fuse, graph, variant, border="zero") -> Engine:
+    key = (w, h, ch, flt.taps, flt.divisor, device, fuse, graph, variant, border)
     eng = _ENGINES.get(key)
     if eng is None:
-        eng = Engine(w, h, ch, flt, device=device, fuse=fuse, graph=graph, variant=variant)
+        eng = Engine(w, h, ch, flt, device=device, fuse=fuse, graph=graph, variant=variant, border=border)
         _ENGINES[key] = eng
         while len(_ENGINES) > _MAX_CACHED:
             _ENGINES.popitem(last=False)
@@ -124,8 +127,13 @@ def _default_backend() -> str:
 
 
 def convolve(image, reps: int = 1, filter="gaussian", backend: str = "auto", device: Optional[int] = None,
-             fuse: Optional[int] = None, graph: bool = False, variant: str = "auto", threads: int = 0):
-    """Apply ``reps`` zero-padded 3x3 convolutions to an 8-bit image.
+             fuse: Optional[int] = None, graph: bool = False, variant: str = "auto", threads: int = 0,
+             border: str = "zero"):
+    """Apply ``reps`` 3x3 convolutions to an 8-bit image.
+
+    ``border``: what a tap reads outside the image — ``"zero"`` (default, the
+    reference's zero padding) or ``"replicate"`` (the nearest image pixel: no
+    dark frame after many repetitions), on every backend.
 
     Returns the same container type as the input (NumPy array or torch tensor
     on the same device).
@@ -133,6 +141,7 @@ def convolve(image, reps: int = 1, filter="gaussian", backend: str = "auto", dev
     if reps < 0:
         raise ValueError("reps must be >= 0")
     flt = get_filter(filter)
+    check_border(border)
     is_tensor = isinstance(image, torch.Tensor)
     if is_tensor and image.dtype != torch.uint8:
         raise TypeError("image tensor must be uint8")
@@ -142,7 +151,7 @@ def convolve(image, reps: int = 1, filter="gaussian", backend: str = "auto", dev
 
     if backend == "numpy":
         arr = image.cpu().numpy() if is_tensor else np.asarray(image)
-        out = numpy_convolve(arr, reps, flt)
+        out = numpy_convolve(arr, reps, flt, border)
         return torch.from_numpy(out).to(image.device) if is_tensor else out
 
     if backend in ("cpu", "omp"):
@@ -150,27 +159,28 @@ def convolve(image, reps: int = 1, filter="gaussian", backend: str = "auto", dev
         arr = np.ascontiguousarray(image.cpu().numpy() if is_tensor else image, dtype=np.uint8)
         out = np.empty_like(arr)
         n.cpu_convolve(arr.reshape(-1), out.reshape(-1), w, h, ch, int(reps), flt.to_native(), backend == "omp",
-                       int(threads))
+                       int(threads), border=border)
         return torch.from_numpy(out).to(image.device) if is_tensor else out
 
     if backend == "hip":
         if device is None:
             device = image.device.index if (is_tensor and image.is_cuda) else 0
-        eng = _cached_engine(w, h, ch, flt, int(device or 0), fuse, graph, variant)
+        eng = _cached_engine(w, h, ch, flt, int(device or 0), fuse, graph, variant, border)
         return eng(image, reps)
 
     raise ValueError(f"unknown backend {backend!r} (hip|omp|cpu|numpy|auto)")
 
 
 def convolve_file(path: str, width: int, height: int, reps: int, channels: str = "grey", filter="gaussian",
-                  out: Optional[str] = None, backend: str = "auto", device: Optional[int] = None) -> str:
+                  out: Optional[str] = None, backend: str = "auto", device: Optional[int] = None,
+                  border: str = "zero") -> str:
     """The reference program in one call (``cuda/main.c:10-53``): read the raw
     image, ``reps`` repetitions, write ``blur_<name>`` (or ``out``); returns the
     output path."""
     from ..utils.raw_io import output_path_for, read_raw, write_raw
 
     img = read_raw(path, width, height, channels)
-    res = convolve(img, reps, filter, backend=backend, device=device)
+    res = convolve(img, reps, filter, backend=backend, device=device, border=border)
     dst = out or output_path_for(path)
     write_raw(dst, res)
     return dst

@@ -23,9 +23,10 @@ from ..models.filters import get_filter
 
 class CpuBandRunner:
     def __init__(self, width: int, height: int, channels: str, filter="gaussian", *, rank: int, world: int,
-                 halo: int = 1, fuse: int = 1, overlap: bool = True, omp: bool = False):
+                 halo: int = 1, fuse: int = 1, overlap: bool = True, omp: bool = False, border: str = "zero"):
         n = require_native()
         self.n = n
+        self.border = border  # rule at the GLOBAL image's edges; band edges exchange halos as ever
         self.width, self.height, self.channels = int(width), int(height), channels
         self.ch = {"grey": 1, "rgb": 3, "rgba": 4}[channels]
         self.row_bytes = self.width * self.ch
@@ -90,13 +91,14 @@ class CpuBandRunner:
             src, dst = self.frames[self.cur], self.frames[self.cur ^ 1]
             for l in ph.launches:
                 self.n.cpu_fused_launch(self.filter, self.channels, self.row_bytes, self.band.rows, self.halo, src, dst,
-                                        l.lo, l.hi, l.steps, self.band.y0, self.height, self.omp)
+                                        l.lo, l.hi, l.steps, self.band.y0, self.height, self.omp,
+                                        border=self.border)
             self.cur ^= 1
 
 
 def local_cpu_cluster_convolve(image: np.ndarray, reps: int, world: int, filter="gaussian", *, halo: int = 1,
                                fuse: int = 1, overlap: bool = True, preload_halo: bool = False,
-                               channels: Optional[str] = None) -> np.ndarray:
+                               channels: Optional[str] = None, border: str = "zero") -> np.ndarray:
     """All `world` bands in this process, halos copied between NumPy frames —
     the CPU twin of the native one-device ``LocalCluster``."""
     img = np.ascontiguousarray(image, dtype=np.uint8)
@@ -104,7 +106,8 @@ def local_cpu_cluster_convolve(image: np.ndarray, reps: int, world: int, filter=
     if channels is None:
         channels = "grey" if img.ndim == 2 else {1: "grey", 3: "rgb", 4: "rgba"}[img.shape[2]]
     rows = img.reshape(h, -1)
-    runs = [CpuBandRunner(w, h, channels, filter, rank=r, world=world, halo=halo, fuse=fuse, overlap=overlap)
+    runs = [CpuBandRunner(w, h, channels, filter, rank=r, world=world, halo=halo, fuse=fuse, overlap=overlap,
+                          border=border)
             for r in range(world)]
     for r in runs:
         r.load(rows[r.band.y0 : r.band.y0 + r.band.rows])
@@ -135,13 +138,14 @@ def local_cpu_cluster_convolve(image: np.ndarray, reps: int, world: int, filter=
             src, dst = r.frames[r.cur], r.frames[r.cur ^ 1]
             for l in plans[k][i].launches:
                 r.n.cpu_fused_launch(r.filter, channels, r.row_bytes, r.band.rows, r.halo, src, dst, l.lo, l.hi,
-                                     l.steps, r.band.y0, h, False)
+                                     l.steps, r.band.y0, h, False, border=border)
             r.cur ^= 1
     return np.concatenate([r.result() for r in runs], axis=0).reshape(img.shape)
 
 
 def distributed_cpu_convolve(image: np.ndarray, reps: int, filter="gaussian", *, halo: int = 1, fuse: int = 1,
-                             overlap: bool = True, group=None, channels: Optional[str] = None) -> np.ndarray:
+                             overlap: bool = True, group=None, channels: Optional[str] = None,
+                             border: str = "zero") -> np.ndarray:
     """Every rank passes the full image; returns the full result on every rank
     (bands gathered with all_gather)."""
     rank = dist.get_rank(group) if dist.is_initialized() else 0
@@ -150,7 +154,8 @@ def distributed_cpu_convolve(image: np.ndarray, reps: int, filter="gaussian", *,
     h, w = img.shape[:2]
     if channels is None:
         channels = "grey" if img.ndim == 2 else {1: "grey", 3: "rgb", 4: "rgba"}[img.shape[2]]
-    run = CpuBandRunner(w, h, channels, filter, rank=rank, world=world, halo=halo, fuse=fuse, overlap=overlap)
+    run = CpuBandRunner(w, h, channels, filter, rank=rank, world=world, halo=halo, fuse=fuse, overlap=overlap,
+                        border=border)
     rows = img.reshape(h, -1)
     run.load(rows[run.band.y0 : run.band.y0 + run.band.rows])
     run.run(reps, group)

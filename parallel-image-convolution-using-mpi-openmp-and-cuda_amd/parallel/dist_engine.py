@@ -78,7 +78,8 @@ class DistributedBlur:
                  ipc_timeout_s: float = 30.0, ipc_pull: str = "grid", cu_mask_queues: bool = True,
                  head_on_slot_streams: bool = True, stream_min_bytes: Optional[int] = None,
                  head_alt_uploads: bool = True, qualify_staging: bool = True, flush_staging: bool = True,
-                 stream_weights: Optional[Sequence[int]] = None, lazy_head: Optional[bool] = None):
+                 stream_weights: Optional[Sequence[int]] = None, lazy_head: Optional[bool] = None,
+                 border: str = "zero"):
         """Pipeline policy (native EngineOptions, echoed by bench.py's JSON
         config): `cu_mask_queues` puts every slot stream on its own hardware
         queue; `head_on_slot_streams` runs a streamed head image's copies on
@@ -97,7 +98,9 @@ class DistributedBlur:
         them out of every CPU cache — the copy engines' reads of lines left
         dirty in the caches of the cores that wrote them (the OpenMP writers
         of load_synthetic) ran that buffer's uploads 5-15 % slower for the
-        life of the process (profiles/r06/e/)."""
+        life of the process (profiles/r06/e/).  `border`: the rule at the
+        GLOBAL image's edges (zero | replicate), applied by every rank's
+        kernels; band edges exchange halos either way."""
         n = require_native()
         ctx = env_context()
         self.rank = ctx.rank if rank is None else int(rank)
@@ -115,7 +118,9 @@ class DistributedBlur:
         # and D2H of ONE image overlap; schedule.hpp plan_streamed)
         if stream_weights:
             stream_chunks = len(stream_weights)
+        self.border = border
         kw = dict(halo=int(halo), fuse=int(fuse), overlap=bool(overlap), variant=variant, slots=int(slots),
+                  border=border,
                   concurrent=int(concurrent), stream_chunks=int(stream_chunks),
                   cu_mask_queues=bool(cu_mask_queues), head_on_slot_streams=bool(head_on_slot_streams),
                   head_alt_uploads=bool(head_alt_uploads),

@@ -80,6 +80,8 @@ def parse(argv: List[str]) -> argparse.Namespace:
     p.add_argument("channels", choices=sorted(_CH))
     p.add_argument("--backend", choices=["hip", "omp", "cpu"], default="hip")
     p.add_argument("--filter", default="gaussian", choices=list_filters())
+    p.add_argument("--border", default="zero", choices=["zero", "replicate"],
+                   help="what a tap reads outside the image: zeros (the reference's rule) or the nearest pixel")
     p.add_argument("--halo", type=int, default=None, help="ghost rows exchanged at once (default: auto)")
     p.add_argument("--fuse", type=int, default=None, help="repetitions per kernel launch (default: auto)")
     p.add_argument("--no-overlap", action="store_true")
@@ -121,7 +123,7 @@ class _HipBand:
         fuse = a.fuse if a.fuse is not None else n.auto_fuse(nf, "auto", frame, _CH[a.channels])
         halo = a.halo if a.halo is not None else auto_halo(a.height, world, a.reps, fuse)
         self.eng = n.BandEngine(a.width, a.height, a.channels, nf, rank, world, device, halo=int(halo),
-                                fuse=int(fuse), overlap=not a.no_overlap)
+                                fuse=int(fuse), overlap=not a.no_overlap, border=a.border)
         self.band, self.halo, self.fuse = self.eng.band, self.eng.halo, self.eng.fuse
         self.comm = self.transport = None
         self.timeout_s = float(a.timeout)
@@ -170,7 +172,7 @@ class _CpuBand:
         fuse = a.fuse if a.fuse is not None else 1
         halo = a.halo if a.halo is not None else auto_halo(a.height, world, a.reps, fuse)
         self.r = CpuBandRunner(a.width, a.height, a.channels, a.filter, rank=rank, world=world, halo=halo, fuse=fuse,
-                               overlap=not a.no_overlap, omp=omp)
+                               overlap=not a.no_overlap, omp=omp, border=a.border)
         self.band, self.halo, self.fuse = self.r.band, self.r.halo, self.r.fuse
         self._preloaded = False
 
@@ -284,7 +286,7 @@ def main(argv: Optional[List[str]] = None) -> int:
                     n.read_raw(a.image, src, a.width, a.height, a.channels)
                 ref = np.empty_like(src)
                 n.cpu_convolve(src, ref, a.width, a.height, a.channels, a.reps, get_filter(a.filter).to_native(),
-                               True, 0)
+                               True, 0, border=a.border)
                 got = np.empty_like(src)
                 n.read_raw(out_path, got, a.width, a.height, a.channels)
                 bad = int(np.count_nonzero(got != ref))
@@ -296,7 +298,7 @@ def main(argv: Optional[List[str]] = None) -> int:
                 px = a.width * a.height * a.reps
                 print(json.dumps({
                     "backend": a.backend, "ranks": world, "width": a.width, "height": a.height,
-                    "channels": a.channels, "reps": a.reps, "filter": a.filter, "loop_s": t_max,
+                    "channels": a.channels, "reps": a.reps, "filter": a.filter, "border": a.border, "loop_s": t_max,
                     "mpix_per_s": px / t_max / 1e6 if t_max > 0 else 0.0, "halo": int(runner.halo),
                     "fuse": int(runner.fuse), "transport": (a.transport if a.backend == "hip" else "gloo") if world > 1 else None,
                     "preload_halo": preload, "launches": launches, "exchanges": exchanges, "output": out_path,

@@ -61,7 +61,8 @@ class ServiceClient:
     def run(self, image: str, width: int, height: int, reps: int, channels: str = "grey",
             out: Optional[str] = None, **flags) -> Dict:
         """One job with the CLI's contract; keyword flags map to `--flag value`
-        (`check=True` -> `--check`).  Paths are resolved here, as the server's
+        (`check=True` -> `--check`, `border="replicate"` -> `--border replicate`;
+        the server keeps one engine per border rule).  Paths are resolved here, as the server's
         working directory is its own.  Raises ServiceError on a failed job."""
         synthetic = flags.get("synthetic") is not None
         argv: List[str] = ["conv", image if synthetic else os.path.abspath(image), str(width), str(height),
