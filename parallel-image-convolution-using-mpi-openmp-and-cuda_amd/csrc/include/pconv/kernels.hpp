@@ -21,6 +21,8 @@
 #include <hip/hip_runtime_api.h>
 
 #include <cstdint>
+#include <utility>
+#include <vector>
 
 #include "pconv/filter.hpp"
 #include "pconv/image.hpp"
@@ -71,12 +73,8 @@ void prepare_stencil(const Filter& f, Channels ch, const StencilLaunch& a, hipSt
 // in one launch (kernels/stencil_float.hip): box/9, edge/28, custom filters.
 void launch_float_temporal(const Filter& f, Channels ch, const StencilLaunch& a, hipStream_t stream);
 // Tune the float kernel's tile shape for this launch geometry now (before a
-// graph capture); clear the cache of tuned shapes.
+// graph capture).
 void prepare_float_temporal(const Filter& f, Channels ch, const StencilLaunch& a, hipStream_t stream);
-void clear_float_tuning();
-// Force the float kernel's tile (m rows per wave, nw waves; m = 0: the model
-// / tuner again).  An unknown shape is ignored.
-void set_float_shape(int m, int nw);
 
 // Whether `v` (or Auto) can fuse `steps` > 1 for this filter.
 bool supports_fusion(const Filter& f, KernelVariant v);
@@ -105,10 +103,41 @@ void launch_fill_zero(uint8_t* p, int64_t bytes, hipStream_t stream);
 // calls it from a helper thread while it creates its first hardware queue).
 void preload_kernel_module();
 
+// ---- Tile shapes and their first-use tuning, for both temporal kernels ----
+// Each family's shapes are one constexpr table in its translation unit; the
+// lists below, the launch dispatch and the tuners' candidates all come from it.
+
+// Tile of the SWAR kernel: lw bytes per lane per strip (4 or 8), m rows per
+// wave, nw waves stacked vertically per workgroup.
+struct SwarShape {
+  int lw = 8, m = 8, nw = 8;
+};
+// Tile of the float temporal kernel: m rows per wave (8 bytes per lane), nw waves.
+struct FloatShape {
+  int m, nw;
+};
+// The instantiated shapes: the SWAR tile kernel's, those of them the buffer-op
+// kernel k_swar_pf has too, and the float kernel's (largest tile first).
+std::vector<SwarShape> swar_shapes();
+std::vector<SwarShape> swar_prefetch_shapes();
+std::vector<FloatShape> float_shapes();
+
 // Empirical tile-shape tuning on / off (off: the latency model's pick);
 // returns the previous setting.  A one-shot process turns it off: timing a
 // dozen candidates costs more than the loop they would speed up.
 bool set_shape_tuning(bool on);
 bool shape_tuning_enabled();
+// How many of the model's best SWAR shapes the tuner times (default 6).
+void set_tune_candidates(int n);
+// Force a tile shape.  SWAR: lw = 0 restores the model, an unknown shape is an
+// error.  Float: m = 0 restores the model / tuner, an unknown shape is ignored.
+void set_swar_shape(int lw, int m, int nw);
+void set_float_shape(int m, int nw);
+// Forget the tuned shapes: of both kernels, of the float kernel alone.
+void clear_swar_tuning();
+void clear_float_tuning();
+// Tuned SWAR entries: ({channels, steps, rows, row_bytes, step_form, kernel}, shape); kernel 0: the tile
+// kernel k_swar, 1: the buffer-op tile kernel k_swar_pf.
+std::vector<std::pair<std::vector<int64_t>, SwarShape>> swar_tuned();
 
 }  // namespace pconv

@@ -22,6 +22,7 @@
 #include "pconv/kernels.hpp"
 #include "pconv/device.hpp"
 #include "swar.hpp"
+#include "tuning.hpp"
 
 namespace pconv {
 namespace {
@@ -286,26 +287,40 @@ int auto_fuse(const Filter& f, KernelVariant v, int64_t frame_bytes, int channel
   return 8;
 }
 
+namespace {
 
-void prepare_stencil(const Filter& f, Channels ch, const StencilLaunch& a_in, hipStream_t stream, KernelVariant v) {
-  StencilLaunch a = a_in;
+// What prepare_stencil and launch_stencil agree on before anything else:
+// rows outside the global image stay zero, so the output region is clipped to
+// it (false: nothing is left), and Auto becomes a kernel.
+//   The single-step kernels take their boundary from the frame's zero pad: a
+// non-zero border runs on the temporal kernels for every step count (an
+// int_exact filter is bit-identical in the float kernel by definition).
+bool resolve_launch(const Filter& f, StencilLaunch& a, KernelVariant& v) {
   a.r0 = std::max(a.r0, -a.g_row0);
   a.r1 = std::min(a.r1, a.height - a.g_row0);
-  if (a.r1 <= a.r0) return;
-  // a non-zero border exists in the temporal kernels only: every step count goes there
+  if (a.r1 <= a.r0) return false;
   const bool fused = a.steps > 1 || a.border != Border::Zero;
-  if (v == KernelVariant::Auto && f.binomial121 && fused) v = KernelVariant::Temporal;
-  if (v == KernelVariant::Auto && !f.binomial121 && fused) v = KernelVariant::FloatTemporal;
-  if (v == KernelVariant::Temporal && f.binomial121 && a.steps <= kMaxFusedSteps) prepare_swar(a, ch, stream);
-  if (v == KernelVariant::FloatTemporal && a.steps <= kMaxFusedSteps) prepare_float_temporal(f, ch, a, stream);
+  if (v == KernelVariant::Auto)
+    v = f.binomial121 ? (fused ? KernelVariant::Temporal : KernelVariant::Binomial)
+                      : (fused ? KernelVariant::FloatTemporal
+                               : (f.int_exact ? KernelVariant::Int9 : KernelVariant::Float9));
+  return true;
+}
+
+}  // namespace
+
+// Silent where launch_stencil would refuse: only a launch the temporal kernels
+// will take has a choice to settle.
+void prepare_stencil(const Filter& f, Channels ch, const StencilLaunch& a_in, hipStream_t stream, KernelVariant v) {
+  StencilLaunch a = a_in;
+  if (!resolve_launch(f, a, v) || a.steps > kMaxFusedSteps) return;
+  if (v == KernelVariant::Temporal && f.binomial121) prepare_swar(a, ch, stream);
+  if (v == KernelVariant::FloatTemporal) prepare_float_temporal(f, ch, a, stream);
 }
 
 void launch_stencil(const Filter& f, Channels ch, const StencilLaunch& a_in, hipStream_t stream, KernelVariant v) {
-  // Rows outside the global image stay zero: clip the output region to it.
   StencilLaunch a = a_in;
-  a.r0 = std::max(a.r0, -a.g_row0);
-  a.r1 = std::min(a.r1, a.height - a.g_row0);
-  if (a.r1 <= a.r0) return;
+  if (!resolve_launch(f, a, v)) return;
   // Geometry guards: every access of the launch must stay inside the frame.
   PCONV_CHECK(a.src && a.dst && a.src != a.dst, "launch_stencil: bad buffers");
   PCONV_CHECK(a.steps >= 1, "launch_stencil: steps must be >= 1");
@@ -317,14 +332,6 @@ void launch_stencil(const Filter& f, Channels ch, const StencilLaunch& a_in, hip
               "launch_stencil: pitch too small for 16-byte vector access");
   PCONV_CHECK(a.row_bytes < (int64_t(1) << 31) && a.r1 - a.frame_lo < (int64_t(1) << 31),
               "launch_stencil: geometry exceeds 32-bit kernel indices");
-  // The single-step kernels take their boundary from the frame's zero pad: a
-  // non-zero border runs on the temporal kernels for every step count (an
-  // int_exact filter is bit-identical in the float kernel by definition).
-  const bool fused = a.steps > 1 || a.border != Border::Zero;
-  if (v == KernelVariant::Auto)
-    v = f.binomial121 ? (fused ? KernelVariant::Temporal : KernelVariant::Binomial)
-                      : (fused ? KernelVariant::FloatTemporal
-                               : (f.int_exact ? KernelVariant::Int9 : KernelVariant::Float9));
   PCONV_CHECK(a.border == Border::Zero || v == KernelVariant::Temporal || v == KernelVariant::FloatTemporal,
               "launch_stencil: border '" + std::string(border_name(a.border)) + "' not supported by kernel '" +
                   std::string(kernel_variant_name(v)) + "' (temporal and float_temporal only)");
@@ -347,11 +354,7 @@ void launch_stencil(const Filter& f, Channels ch, const StencilLaunch& a_in, hip
     PCONV_CHECK(f.binomial121, "binomial kernel requires the gaussian filter");
   if (v == KernelVariant::Int9)
     PCONV_CHECK(f.int_exact && f.abs_sum() * 255 < (1 << 30), "int9 kernel requires an int-exact filter");
-  switch (ch) {
-    case Channels::Grey: launch_ch<1>(f, a, stream, v); break;
-    case Channels::Rgb: launch_ch<3>(f, a, stream, v); break;
-    case Channels::Rgba: launch_ch<4>(f, a, stream, v); break;
-  }
+  with_channels(ch, [&](auto chn) { launch_ch<decltype(chn)::value>(f, a, stream, v); });
   PCONV_HIP_CHECK(hipGetLastError());
 }
 

@@ -37,6 +37,7 @@
 
 #include "pconv/device.hpp"
 #include "pconv/kernels.hpp"
+#include "tuning.hpp"
 
 namespace pconv {
 namespace {
@@ -398,9 +399,44 @@ __global__ __launch_bounds__(64 * NW) void k_float_temporal(const uint8_t* __res
   }
 }
 
-struct FtShape {
-  int m, nw;
+// Instantiated tile shapes (M rows per wave, NW waves), written in this table
+// and nowhere else: float_shapes(), the launch dispatch (launch_ft_with:
+// compiled for every row, so a row is an instantiation), the model's
+// candidates and the tuner's all read it.  Largest tiles (least halo) first,
+// and the order is behaviour: pick_ft_shape returns the first shape that fills
+// the chip, and {16,4} and {8,8} tie on workgroup count.
+constexpr FloatShape kFtShapes[] = {{16, 8}, {16, 4}, {8, 8}, {8, 4}, {4, 8}};
+constexpr size_t kNumFtShapes = sizeof(kFtShapes) / sizeof(kFtShapes[0]);
+
+// Row of the table that holds a shape; kNumFtShapes: not instantiated.
+size_t ft_shape_index(int m, int nw) {
+  size_t i = 0;
+  while (i < kNumFtShapes && (kFtShapes[i].m != m || kFtShapes[i].nw != nw)) ++i;
+  return i;
+}
+
+// Grid of one launch of a tile shape: the host's one copy of the quantities
+// the kernel derives from (steps, CH, M, NW), for the launch, the model and
+// the tuner's candidate test.
+struct FtGeom {
+  bool ok = false;  // the halo leaves valid output (vlanes, vrows > 0)
+  int hl = 0;       // halo lanes per side
+  int vlanes = 0;   // valid 8-byte output chunks per strip
+  int vrows = 0;    // valid output rows per tile
+  int64_t col_tiles = 0, row_tiles = 0;
 };
+
+FtGeom ft_geom(const FloatShape& sh, int ch, int steps, int64_t rows, int64_t row_bytes) {
+  FtGeom g;
+  g.hl = (steps * ch + 7) / 8;
+  g.vlanes = 64 - 2 * g.hl;
+  g.vrows = sh.m * sh.nw - 2 * steps;
+  g.ok = g.vlanes > 0 && g.vrows > 0;
+  if (!g.ok) return g;
+  g.col_tiles = ceil_div<int64_t>(ceil_div<int64_t>(row_bytes, 8), g.vlanes);
+  g.row_tiles = ceil_div<int64_t>(rows, g.vrows);
+  return g;
+}
 
 // Tile shape when nothing is tuned (one-shot CLI, a capture before tuning):
 // the largest tile (least halo) whose grid fills the chip — at least 3/4 of
@@ -411,12 +447,10 @@ struct FtShape {
 // 16x8 (best).  set_float_shape(M, NW) forces one.
 std::atomic<int> g_ft_force_m{0}, g_ft_force_nw{0};
 
-FtShape pick_ft_shape(int steps, int ch, int64_t rows, int64_t row_bytes) {
-  static const FtShape cands[] = {{16, 8}, {16, 4}, {8, 8}, {8, 4}, {4, 8}};  // largest tiles first
+FloatShape pick_ft_shape(int steps, int ch, int64_t rows, int64_t row_bytes) {
   if (const int fm = g_ft_force_m.load(std::memory_order_relaxed)) {
-    const int fnw = g_ft_force_nw.load(std::memory_order_relaxed);
-    for (const auto& c : cands)
-      if (c.m == fm && c.nw == fnw) return c;
+    const size_t i = ft_shape_index(fm, g_ft_force_nw.load(std::memory_order_relaxed));
+    if (i < kNumFtShapes) return kFtShapes[i];
   }
   static int cus = [] {
     int dev = 0, n = 0;
@@ -425,14 +459,12 @@ FtShape pick_ft_shape(int steps, int ch, int64_t rows, int64_t row_bytes) {
       n = 256;
     return std::max(1, n);
   }();
-  const int hl = (steps * ch + 7) / 8;
-  const int64_t ctiles = ceil_div<int64_t>(ceil_div<int64_t>(row_bytes, 8), std::max(1, 64 - 2 * hl));
-  FtShape most{4, 8};
+  FloatShape most = kFtShapes[kNumFtShapes - 1];  // the smallest tile
   int64_t most_wgs = -1;
-  for (const auto& c : cands) {
-    const int vrows = c.m * c.nw - 2 * steps;
-    if (vrows <= 0) continue;
-    const int64_t wgs = ctiles * ceil_div<int64_t>(rows, vrows);
+  for (const auto& c : kFtShapes) {
+    const FtGeom g = ft_geom(c, ch, steps, rows, row_bytes);
+    if (!g.ok) continue;
+    const int64_t wgs = g.col_tiles * g.row_tiles;
     const int64_t rounds = ceil_div<int64_t>(wgs, cus);
     if (4 * wgs >= 3 * static_cast<int64_t>(cus) && 4 * wgs >= 3 * rounds * cus) return c;
     if (wgs > most_wgs) {
@@ -445,40 +477,29 @@ FtShape pick_ft_shape(int steps, int ch, int64_t rows, int64_t row_bytes) {
 
 template <int CH, bool UNIFORM, int M, int NW>
 void launch_ft_shape(const StencilLaunch& a, const FloatTaps& tp, hipStream_t s) {
-  const int steps = a.steps;
-  const int hl = (steps * CH + 7) / 8;
-  const int vlanes = 64 - 2 * hl;
-  const int vrows = M * NW - 2 * steps;
-  PCONV_CHECK(vlanes > 0 && vrows > 0, "float temporal kernel: steps too large for the tile");
-  const int nchunks = static_cast<int>(ceil_div<int64_t>(a.row_bytes, 8));
-  const dim3 grid(ceil_div(nchunks, vlanes), ceil_div(static_cast<int>(a.r1 - a.r0), vrows));
+  const FtGeom g = ft_geom(FloatShape{M, NW}, CH, a.steps, a.r1 - a.r0, a.row_bytes);
+  PCONV_CHECK(g.ok, "float temporal kernel: steps too large for the tile");
+  const dim3 grid(static_cast<unsigned>(g.col_tiles), static_cast<unsigned>(g.row_tiles));
   const auto kern = a.border == Border::Replicate ? &k_float_temporal<CH, UNIFORM, M, NW, true>
                                                   : &k_float_temporal<CH, UNIFORM, M, NW, false>;
   kern<<<grid, dim3(64 * NW), 0, s>>>(
-      a.src, a.dst, a.pitch, static_cast<int>(a.row_bytes), static_cast<int>(a.r0), static_cast<int>(a.r1), steps,
+      a.src, a.dst, a.pitch, static_cast<int>(a.row_bytes), static_cast<int>(a.r0), static_cast<int>(a.r1), a.steps,
       static_cast<int>(a.g_row0), static_cast<int>(std::min<int64_t>(a.height, int64_t(1) << 30)), tp);
 }
 
 template <int CH, bool UNIFORM>
-void launch_ft_with(const StencilLaunch& a, const FloatTaps& tp, hipStream_t s, FtShape sh) {
-#define PCONV_FT(M_, NW_)                                  \
-  if (sh.m == M_ && sh.nw == NW_) {                        \
-    launch_ft_shape<CH, UNIFORM, M_, NW_>(a, tp, s);       \
-    return;                                                \
-  }
-  PCONV_FT(16, 8)
-  PCONV_FT(8, 8)
-  PCONV_FT(16, 4)
-  PCONV_FT(8, 4)
-  PCONV_FT(4, 8)
-#undef PCONV_FT
-  PCONV_FAIL("float temporal kernel: unsupported tile shape");
+void launch_ft_with(const StencilLaunch& a, const FloatTaps& tp, hipStream_t s, FloatShape sh) {
+  const bool known = with_index<kNumFtShapes>(ft_shape_index(sh.m, sh.nw), [&](auto i) {
+    constexpr FloatShape S = kFtShapes[decltype(i)::value];
+    launch_ft_shape<CH, UNIFORM, S.m, S.nw>(a, tp, s);
+  });
+  PCONV_CHECK(known, "float temporal kernel: unsupported tile shape");
 }
 
 // Empirical shape tuning, as for the SWAR kernel (stencil_swar.hip): on the
-// first launch of a geometry every candidate runs the REAL launch (same src
-// -> dst, so repeats write the same bytes) in two interleaved timed passes and
-// the fastest is cached per (channels, uniform, steps, rows, row bytes).  The
+// first launch of a geometry every shape that runs it is timed on the REAL
+// launch (fastest_candidate, tuning.hpp) and the fastest is cached per
+// (channels, uniform, steps, rows, row bytes).  The
 // shape is a large lever on these small frames and not monotonic in the
 // model (1920x2520 RGB box, 4 steps: 8.0 us/rep with 16x8 tiles, 9.2-10.4
 // with the others; gpurun_out/r03/g/float_sweep.jsonl).  Never while the
@@ -493,44 +514,26 @@ struct FtKey {
   }
 };
 std::mutex g_ft_mu;
-std::map<FtKey, FtShape> g_ft_tuned;
-
-bool capturing_ft(hipStream_t s) {
-  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-  return hipStreamIsCapturing(s, &st) == hipSuccess && st != hipStreamCaptureStatusNone;
-}
+std::map<FtKey, FloatShape> g_ft_tuned;
 
 template <int CH, bool UNIFORM>
-FtShape tuned_ft_shape(const StencilLaunch& a, const FloatTaps& tp, hipStream_t s) {
-  const FtShape model = pick_ft_shape(a.steps, CH, a.r1 - a.r0, a.row_bytes);
+FloatShape tuned_ft_shape(const StencilLaunch& a, const FloatTaps& tp, hipStream_t s) {
+  const int64_t rows = a.r1 - a.r0;
+  const FloatShape model = pick_ft_shape(a.steps, CH, rows, a.row_bytes);
   if (g_ft_force_m.load(std::memory_order_relaxed) || !shape_tuning_enabled()) return model;
-  const FtKey key{CH, UNIFORM, a.steps, a.r1 - a.r0, a.row_bytes};
+  const FtKey key{CH, UNIFORM, a.steps, rows, a.row_bytes};
   {
     std::lock_guard<std::mutex> lk(g_ft_mu);
     auto it = g_ft_tuned.find(key);
     if (it != g_ft_tuned.end()) return it->second;
   }
-  if (capturing_ft(s)) return model;
-  static const FtShape cands[] = {{16, 8}, {8, 8}, {16, 4}, {8, 4}, {4, 8}};
-  std::vector<FtShape> ok;
-  for (const auto& c : cands)
-    if (c.m * c.nw - 2 * a.steps > 0) ok.push_back(c);
+  if (stream_capturing(s)) return model;
+  std::vector<FloatShape> ok;
+  for (const auto& c : kFtShapes)
+    if (ft_geom(c, CH, a.steps, rows, a.row_bytes).ok) ok.push_back(c);
   PCONV_CHECK(!ok.empty(), "float temporal kernel: steps too large for every tile shape");
-  FtShape best = ok.front();
-  if (ok.size() > 1) {
-    Event e0 = Event::create(true), e1 = Event::create(true);
-    std::vector<float> t(ok.size(), 1e30f);
-    for (int pass = 0; pass < 2; ++pass)
-      for (size_t i = 0; i < ok.size(); ++i) {
-        if (pass == 0) launch_ft_with<CH, UNIFORM>(a, tp, s, ok[i]);  // warm
-        e0.record(s);
-        for (int r = 0; r < 3; ++r) launch_ft_with<CH, UNIFORM>(a, tp, s, ok[i]);
-        e1.record(s);
-        PCONV_HIP_CHECK(hipEventSynchronize(e1.get()));
-        t[i] = std::min(t[i], Event::elapsed_ms(e0, e1));
-      }
-    best = ok[std::min_element(t.begin(), t.end()) - t.begin()];
-  }
+  const FloatShape best =
+      ok[fastest_candidate(ok.size(), s, [&](size_t i) { launch_ft_with<CH, UNIFORM>(a, tp, s, ok[i]); })];
   std::lock_guard<std::mutex> lk(g_ft_mu);
   g_ft_tuned.emplace(key, best);
   return best;
@@ -538,37 +541,27 @@ FtShape tuned_ft_shape(const StencilLaunch& a, const FloatTaps& tp, hipStream_t 
 
 template <int CH, bool UNIFORM>
 void launch_ft(const StencilLaunch& a, const FloatTaps& tp, hipStream_t s, bool launch) {
-  const FtShape sh = tuned_ft_shape<CH, UNIFORM>(a, tp, s);
+  const FloatShape sh = tuned_ft_shape<CH, UNIFORM>(a, tp, s);
   if (launch) launch_ft_with<CH, UNIFORM>(a, tp, s, sh);
 }
 
-template <int CH>
-void launch_ft_ch(const Filter& f, const StencilLaunch& a, hipStream_t s, bool launch) {
+void float_temporal(const Filter& f, Channels ch, const StencilLaunch& a, hipStream_t stream, bool launch) {
+  PCONV_CHECK(a.steps >= 1 && a.steps <= kMaxFusedSteps, "float temporal kernel: steps out of range");
+  PCONV_CHECK(a.height < (int64_t(1) << 30) && a.g_row0 < (int64_t(1) << 30), "float temporal kernel: rows exceed 2^30");
+  PCONV_CHECK(a.row_bytes > 0 && a.row_bytes < (int64_t(1) << 30), "float temporal kernel: row bytes out of range");
   FloatTaps tp;
   bool uniform = true;
   for (int i = 0; i < 9; ++i) {
     tp.w[i] = f.weights[i];
     uniform = uniform && f.weights[i] == f.weights[0];
   }
-  if (uniform)
-    launch_ft<CH, true>(a, tp, s, launch);
-  else
-    launch_ft<CH, false>(a, tp, s, launch);
-}
-
-}  // namespace
-
-namespace {
-
-void float_temporal(const Filter& f, Channels ch, const StencilLaunch& a, hipStream_t stream, bool launch) {
-  PCONV_CHECK(a.steps >= 1 && a.steps <= kMaxFusedSteps, "float temporal kernel: steps out of range");
-  PCONV_CHECK(a.height < (int64_t(1) << 30) && a.g_row0 < (int64_t(1) << 30), "float temporal kernel: rows exceed 2^30");
-  PCONV_CHECK(a.row_bytes > 0 && a.row_bytes < (int64_t(1) << 30), "float temporal kernel: row bytes out of range");
-  switch (ch) {
-    case Channels::Grey: launch_ft_ch<1>(f, a, stream, launch); break;
-    case Channels::Rgb: launch_ft_ch<3>(f, a, stream, launch); break;
-    case Channels::Rgba: launch_ft_ch<4>(f, a, stream, launch); break;
-  }
+  with_channels(ch, [&](auto chn) {
+    constexpr int CH = decltype(chn)::value;
+    if (uniform)
+      launch_ft<CH, true>(a, tp, stream, launch);
+    else
+      launch_ft<CH, false>(a, tp, stream, launch);
+  });
 }
 
 }  // namespace
@@ -579,6 +572,10 @@ void launch_float_temporal(const Filter& f, Channels ch, const StencilLaunch& a,
 
 void prepare_float_temporal(const Filter& f, Channels ch, const StencilLaunch& a, hipStream_t stream) {
   float_temporal(f, ch, a, stream, false);
+}
+
+std::vector<FloatShape> float_shapes() {
+  return std::vector<FloatShape>(std::begin(kFtShapes), std::end(kFtShapes));
 }
 
 void set_float_shape(int m, int nw) {

@@ -49,12 +49,15 @@
 #include <atomic>
 #include <map>
 #include <mutex>
+#include <string>
 #include <tuple>
 #include <type_traits>
+#include <vector>
 
 #include "pconv/device.hpp"
 #include "swar.hpp"
 #include "swar_device.hpp"
+#include "tuning.hpp"
 
 namespace pconv {
 namespace {
@@ -282,21 +285,58 @@ __global__ __launch_bounds__(64 * NW) void k_swar_pf(const uint8_t* __restrict__
   }
 }
 
-// Instantiated tile shapes (LW, M, NW).  Taller tiles for large frames
+// Instantiated tile shapes (LW, M, NW), each written in this table and nowhere
+// else: swar_shapes(), the launch and resource dispatch (launch_choice,
+// query_res: compiled for every row, so a row is an instantiation) and the
+// candidates of the model and the tuner all read it.  `pf`: the buffer-op
+// kernel k_swar_pf has the shape too; {4,8,8} is the first such row — what
+// forced buffer-op mode falls back to (it runs every steps <= 16).
+//   Taller tiles for large frames
 // (fewer ghost rows per tile) were built and timed on 32768^2 grey at fuse 12
 // in round 6 and all lost to {4,20,8} (105.4 us/rep): {4,24,8} 110.4-141.6
 // (3 waves/SIMD), {4,16,16} 133-137, {4,20,16} 126.6-135.8 (one 16-wave
 // workgroup per CU: barrier across 16 waves); profiles/r06/b/shape_sweep.jsonl.
-constexpr SwarShape kShapes[] = {
-    {8, 8, 8}, {8, 8, 4}, {8, 16, 4}, {8, 4, 8},              // 8-byte lanes: large images
-    {4, 8, 8}, {4, 6, 8}, {4, 5, 8}, {4, 4, 8}, {4, 3, 8}, {4, 4, 16},  // 4-byte lanes: small bands
-    {4, 2, 16}, {4, 3, 16}, {8, 2, 16}, {8, 4, 16},                     // 16 waves: latency-bound bands
-    {4, 16, 4}, {4, 12, 4}, {4, 16, 8}, {4, 12, 8},                     // tall waves: fewer halo rows per tile
-    {4, 20, 8},
+struct Tile {
+  SwarShape shape;
+  bool pf;
 };
+constexpr Tile kTiles[] = {
+    // 8-byte lanes: large images
+    {{8, 8, 8}, false}, {{8, 8, 4}, false}, {{8, 16, 4}, false}, {{8, 4, 8}, false},
+    // 4-byte lanes: small bands
+    {{4, 8, 8}, true}, {{4, 6, 8}, false}, {{4, 5, 8}, false}, {{4, 4, 8}, false}, {{4, 3, 8}, false},
+    {{4, 4, 16}, false},
+    // 16 waves: latency-bound bands
+    {{4, 2, 16}, false}, {{4, 3, 16}, false}, {{8, 2, 16}, false}, {{8, 4, 16}, false},
+    // tall waves: fewer halo rows per tile
+    {{4, 16, 4}, true}, {{4, 12, 4}, true}, {{4, 16, 8}, true}, {{4, 12, 8}, true},
+    {{4, 20, 8}, true},
+};
+constexpr size_t kNumTiles = sizeof(kTiles) / sizeof(kTiles[0]);
+
+constexpr bool pf_tiles_have_4_byte_lanes() {
+  for (const auto& t : kTiles)
+    if (t.pf && t.shape.lw != 4) return false;
+  return true;
+}
+static_assert(pf_tiles_have_4_byte_lanes(), "k_swar_pf is written for 4-byte lanes");
+
+// Row of the table that holds a shape; kNumTiles: not instantiated.
+size_t tile_index(const SwarShape& s) {
+  size_t i = 0;
+  while (i < kNumTiles && (kTiles[i].shape.lw != s.lw || kTiles[i].shape.m != s.m || kTiles[i].shape.nw != s.nw)) ++i;
+  return i;
+}
+
+bool known_shape(const SwarShape& s) { return tile_index(s) < kNumTiles; }
+
+bool known_pf_shape(const SwarShape& s) {
+  const size_t i = tile_index(s);
+  return i < kNumTiles && kTiles[i].pf;
+}
 
 // Process-wide kernel settings (set_xcd_swizzle / set_swar_alt /
-// set_prefetch_mode / set_swar_shape / set_autotune / set_tune_candidates;
+// set_prefetch_mode / set_swar_shape / set_shape_tuning / set_tune_candidates;
 // no environment variables).
 std::atomic<int> g_xcd_swizzle{1};  // XCD-aware tile order (neutral +-2 %, kept on)
 
@@ -306,9 +346,13 @@ std::atomic<int> g_alt_mode{-1};  // step form: -1 tuned, else forced 0 / 1 (run
 
 int alt_mode() { return g_alt_mode.load(std::memory_order_relaxed); }
 
-// Step form when nothing was tuned (graph capture, autotune off): the paired
+// Step form when nothing was tuned (graph capture, tuning off): the paired
 // form is faster in most measured geometries.
 int default_form() { return alt_mode() >= 0 ? alt_mode() : 1; }
+
+std::atomic<int> g_pf_mode{-1};  // -1 tune, 0 off, 1 forced
+
+int pf_mode() { return g_pf_mode.load(std::memory_order_relaxed); }
 
 // Kernel of one step form and border rule (the border is a template
 // parameter: the zero-border instantiations are the kernels they always were).
@@ -329,69 +373,31 @@ auto swar_pf_kernel(int form, Border border = Border::Zero) {
   return form >= 1 ? static_cast<F>(&k_swar_pf<CH, M, NW, 1>) : static_cast<F>(&k_swar_pf<CH, M, NW, 0>);
 }
 
-template <int CH, int LW, int M, int NW>
-void launch_one(const StencilLaunch& a, hipStream_t s, int form) {
-  const int steps = a.steps;
-  const int hl = (steps * CH + LW - 1) / LW;
-  const int vbytes = (64 - 2 * hl) * LW;
-  const int vrows = M * NW - 2 * steps;
-  PCONV_CHECK(vbytes > 0 && vrows > 0, "swar temporal kernel: steps too large for the tile");
-  const int nstrips = static_cast<int>(ceil_div<int64_t>(a.row_bytes, vbytes));
-  const int pair_stride = (nstrips + 1) / 2;
-  const int row_tiles = ceil_div(static_cast<int>(a.r1 - a.r0), vrows);
-  const dim3 grid(pair_stride * row_tiles);
-  const int64_t hmax = std::min<int64_t>(a.height, int64_t(1) << 30);
-  swar_kernel<CH, LW, M, NW>(form, a.border)<<<grid, dim3(64 * NW), 0, s>>>(
-      a.src, a.dst, a.pitch, static_cast<int>(a.row_bytes),
-      static_cast<int>(a.r0), static_cast<int>(a.r1), steps, static_cast<int>(a.g_row0), static_cast<int>(hmax), nstrips,
-      pair_stride, row_tiles, xcd_swizzle_enabled() ? 1 : 0);
-}
-
-template <int CH>
-void launch_ch(const StencilLaunch& a, hipStream_t s, SwarShape sh, int form) {
-#define PCONV_SWAR(LW_, M_, NW_)                            \
-  if (sh.lw == LW_ && sh.m == M_ && sh.nw == NW_) {         \
-    launch_one<CH, LW_, M_, NW_>(a, s, form);               \
-    return;                                                 \
-  }
-  PCONV_SWAR(8, 8, 8)
-  PCONV_SWAR(8, 8, 4)
-  PCONV_SWAR(8, 16, 4)
-  PCONV_SWAR(8, 4, 8)
-  PCONV_SWAR(4, 8, 8)
-  PCONV_SWAR(4, 6, 8)
-  PCONV_SWAR(4, 5, 8)
-  PCONV_SWAR(4, 4, 8)
-  PCONV_SWAR(4, 3, 8)
-  PCONV_SWAR(4, 4, 16)
-  PCONV_SWAR(4, 2, 16)
-  PCONV_SWAR(4, 3, 16)
-  PCONV_SWAR(8, 2, 16)
-  PCONV_SWAR(8, 4, 16)
-  PCONV_SWAR(4, 16, 4)
-  PCONV_SWAR(4, 12, 4)
-  PCONV_SWAR(4, 16, 8)
-  PCONV_SWAR(4, 12, 8)
-  PCONV_SWAR(4, 20, 8)
-#undef PCONV_SWAR
-  PCONV_FAIL("swar temporal kernel: unsupported tile shape");
-}
-
-// Buffer-op tile kernel (k_swar_pf): shapes instantiated.
-constexpr SwarShape kPfShapes[] = {
-    {4, 8, 8}, {4, 12, 4}, {4, 16, 4}, {4, 12, 8}, {4, 16, 8}, {4, 20, 8},
+// Grid of one launch of a tile shape: the host's one copy of the quantities
+// the kernels derive from (steps, CH, LW, M, NW), for the launch, the latency
+// model, the tuner's candidate tests and the shape override.
+struct SwarGeom {
+  bool ok = false;  // the halo leaves valid output (vbytes, vrows > 0) and a lane holds a whole pixel
+  int hl = 0;       // halo lanes per side
+  int vbytes = 0;   // valid output bytes per strip
+  int vrows = 0;    // valid output rows per tile
+  int64_t nstrips = 0, pair_stride = 0, row_tiles = 0;
+  int64_t tiles = 0;  // workgroups, pair_stride x row_tiles; > 0: the shape runs the launch
 };
 
-bool known_pf_shape(const SwarShape& s) {
-  for (const auto& k : kPfShapes)
-    if (k.lw == s.lw && k.m == s.m && k.nw == s.nw) return true;
-  return false;
+SwarGeom swar_geom(const SwarShape& sh, int ch, int steps, int64_t rows, int64_t row_bytes) {
+  SwarGeom g;
+  g.hl = (steps * ch + sh.lw - 1) / sh.lw;
+  g.vbytes = (64 - 2 * g.hl) * sh.lw;
+  g.vrows = sh.m * sh.nw - 2 * steps;
+  g.ok = g.vbytes > 0 && g.vrows > 0 && sh.lw >= ch;
+  if (!g.ok) return g;
+  g.nstrips = ceil_div<int64_t>(row_bytes, g.vbytes);
+  g.pair_stride = (g.nstrips + 1) / 2;
+  g.row_tiles = ceil_div<int64_t>(rows, g.vrows);
+  g.tiles = g.pair_stride * g.row_tiles;
+  return g;
 }
-
-std::atomic<int> g_pf_mode{-1};  // -1 tune, 0 off, 1 forced
-
-
-int pf_mode() { return g_pf_mode.load(std::memory_order_relaxed); }
 
 // Launches the prefetch kernel can take: 4-byte lanes, whole dwords per row,
 // source and destination ranges under 2 GiB (32-bit buffer offsets).
@@ -400,52 +406,28 @@ bool pf_launch_ok(const StencilLaunch& a, int steps) {
   return a.row_bytes % 4 == 0 && src_rows * a.pitch < (int64_t(1) << 31) && (a.r1 - a.r0) * dp < (int64_t(1) << 31);
 }
 
-template <int CH, int M, int NW>
-void launch_pf_one(const StencilLaunch& a, hipStream_t s, int form) {
-  const int steps = a.steps;
-  const int hl = (steps * CH + 3) / 4;
-  const int vbytes = (64 - 2 * hl) * 4;
-  const int vrows = M * NW - 2 * steps;
-  PCONV_CHECK(vbytes > 0 && vrows > 0, "swar prefetch kernel: steps too large for the tile");
-  PCONV_CHECK(pf_launch_ok(a, steps), "swar prefetch kernel: needs whole dwords per row and < 2 GiB ranges");
-  const int nstrips = static_cast<int>(ceil_div<int64_t>(a.row_bytes, vbytes));
-  const int pair_stride = (nstrips + 1) / 2;
-  const int row_tiles = ceil_div(static_cast<int>(a.r1 - a.r0), vrows);
-  const int64_t ntiles = int64_t(pair_stride) * row_tiles;
-  PCONV_CHECK(ntiles < (int64_t(1) << 31), "swar prefetch kernel: too many tiles");
-  const int grid = static_cast<int>(ntiles);
-  const int xs = xcd_swizzle_enabled() ? 1 : 0;
+// One launch of row I of the table: the tile kernel, or (PF) the buffer-op one.
+template <int CH, size_t I, bool PF>
+void launch_tile(const StencilLaunch& a, hipStream_t s, int form) {
+  constexpr SwarShape S = kTiles[I].shape;
+  const char* who = PF ? "swar prefetch kernel" : "swar temporal kernel";
+  const SwarGeom g = swar_geom(S, CH, a.steps, a.r1 - a.r0, a.row_bytes);
+  PCONV_CHECK(g.ok, std::string(who) + ": steps too large for the tile");
+  if constexpr (PF)
+    PCONV_CHECK(pf_launch_ok(a, a.steps), std::string(who) + ": needs whole dwords per row and < 2 GiB ranges");
+  PCONV_CHECK(g.tiles < (int64_t(1) << 31), std::string(who) + ": too many tiles");
+  const dim3 grid(static_cast<unsigned>(g.tiles)), block(64 * S.nw);
   const int hmax = static_cast<int>(std::min<int64_t>(a.height, int64_t(1) << 30));
-  swar_pf_kernel<CH, M, NW>(form, a.border)<<<dim3(grid), dim3(64 * NW), 0, s>>>(
-      a.src, a.dst, static_cast<int>(a.pitch), static_cast<int>(a.row_bytes), static_cast<int>(a.r0),
-      static_cast<int>(a.r1), steps, static_cast<int>(a.g_row0), hmax, nstrips, pair_stride, row_tiles, xs);
-}
-
-// Tiles of a launch and the workgroups the prefetch kernel keeps resident.
-int64_t pf_tiles(SwarShape sh, int ch, int steps, int64_t rows, int64_t row_bytes) {
-  const int hl = (steps * ch + sh.lw - 1) / sh.lw;
-  const int vbytes = (64 - 2 * hl) * sh.lw;
-  const int vrows = sh.m * sh.nw - 2 * steps;
-  if (vbytes <= 0 || vrows <= 0 || sh.lw < ch || rows <= 0) return 0;
-  return ((ceil_div<int64_t>(row_bytes, vbytes) + 1) / 2) * ceil_div<int64_t>(rows, vrows);
-}
-
-template <int CH>
-void launch_pf_ch(const StencilLaunch& a, hipStream_t s, SwarShape sh, int form) {
-#define PCONV_PF(LW_, M_, NW_)                       \
-  if (sh.lw == LW_ && sh.m == M_ && sh.nw == NW_) {  \
-    launch_pf_one<CH, M_, NW_>(a, s, form);          \
-    return;                                          \
-  }
-  PCONV_PF(4, 8, 8) PCONV_PF(4, 12, 4) PCONV_PF(4, 16, 4) PCONV_PF(4, 12, 8) PCONV_PF(4, 16, 8) PCONV_PF(4, 20, 8)
-#undef PCONV_PF
-  PCONV_FAIL("swar prefetch kernel: unsupported tile shape");
-}
-
-bool known_shape(const SwarShape& s) {
-  for (const auto& k : kShapes)
-    if (k.lw == s.lw && k.m == s.m && k.nw == s.nw) return true;
-  return false;
+  const auto launch = [&](auto kern, auto pitch) {
+    kern<<<grid, block, 0, s>>>(a.src, a.dst, pitch, static_cast<int>(a.row_bytes), static_cast<int>(a.r0),
+                                static_cast<int>(a.r1), a.steps, static_cast<int>(a.g_row0), hmax,
+                                static_cast<int>(g.nstrips), static_cast<int>(g.pair_stride),
+                                static_cast<int>(g.row_tiles), xcd_swizzle_enabled() ? 1 : 0);
+  };
+  if constexpr (PF)
+    launch(swar_pf_kernel<CH, S.m, S.nw>(form, a.border), static_cast<int>(a.pitch));
+  else
+    launch(swar_kernel<CH, S.lw, S.m, S.nw>(form, a.border), a.pitch);
 }
 
 // Shape override (tuning / tests): set_swar_shape().
@@ -473,7 +455,18 @@ void set_swar_shape(int lw, int m, int nw) {
   g_have_shape = true;
 }
 
-std::vector<SwarShape> swar_shapes() { return std::vector<SwarShape>(std::begin(kShapes), std::end(kShapes)); }
+std::vector<SwarShape> swar_shapes() {
+  std::vector<SwarShape> out;
+  for (const auto& t : kTiles) out.push_back(t.shape);
+  return out;
+}
+
+std::vector<SwarShape> swar_prefetch_shapes() {
+  std::vector<SwarShape> out;
+  for (const auto& t : kTiles)
+    if (t.pf) out.push_back(t.shape);
+  return out;
+}
 
 namespace {
 
@@ -485,33 +478,17 @@ struct KernelRes {
   bool measured = false;
 };
 
-template <int CH>
-KernelRes query_res(SwarShape sh, int form) {
+KernelRes query_res(const SwarShape& sh, int ch, int form) {
   hipFuncAttributes at{};
   hipError_t e = hipErrorInvalidValue;
-#define PCONV_SWAR(LW_, M_, NW_)                                                                     \
-  if (sh.lw == LW_ && sh.m == M_ && sh.nw == NW_)                                                   \
-    e = hipFuncGetAttributes(&at, reinterpret_cast<const void*>(swar_kernel<CH, LW_, M_, NW_>(form)));
-  PCONV_SWAR(8, 8, 8)
-  PCONV_SWAR(8, 8, 4)
-  PCONV_SWAR(8, 16, 4)
-  PCONV_SWAR(8, 4, 8)
-  PCONV_SWAR(4, 8, 8)
-  PCONV_SWAR(4, 6, 8)
-  PCONV_SWAR(4, 5, 8)
-  PCONV_SWAR(4, 4, 8)
-  PCONV_SWAR(4, 3, 8)
-  PCONV_SWAR(4, 4, 16)
-  PCONV_SWAR(4, 2, 16)
-  PCONV_SWAR(4, 3, 16)
-  PCONV_SWAR(8, 2, 16)
-  PCONV_SWAR(8, 4, 16)
-  PCONV_SWAR(4, 16, 4)
-  PCONV_SWAR(4, 12, 4)
-  PCONV_SWAR(4, 16, 8)
-  PCONV_SWAR(4, 12, 8)
-  PCONV_SWAR(4, 20, 8)
-#undef PCONV_SWAR
+  const bool known = with_channels(static_cast<Channels>(ch), [&](auto chn) {
+    return with_index<kNumTiles>(tile_index(sh), [&](auto i) {
+      constexpr SwarShape S = kTiles[decltype(i)::value].shape;
+      e = hipFuncGetAttributes(
+          &at, reinterpret_cast<const void*>(swar_kernel<decltype(chn)::value, S.lw, S.m, S.nw>(form)));
+    });
+  });
+  PCONV_CHECK(known, "swar temporal kernel: unsupported tile shape");
   KernelRes r;
   if (e == hipSuccess && at.numRegs > 0) {
     r.vgpr = at.numRegs;
@@ -525,19 +502,28 @@ KernelRes query_res(SwarShape sh, int form) {
   return r;
 }
 
-KernelRes kernel_res(SwarShape sh, int ch, int form) {
+KernelRes kernel_res(const SwarShape& sh, int ch, int form) {
   static std::mutex mu;
   static std::map<std::tuple<int, int, int, int, int>, KernelRes> cache;
   std::lock_guard<std::mutex> lk(mu);
   const auto key = std::make_tuple(ch, sh.lw, sh.m, sh.nw, form);
   auto it = cache.find(key);
   if (it != cache.end()) return it->second;
-  const KernelRes r = ch == 1 ? query_res<1>(sh, form) : ch == 3 ? query_res<3>(sh, form) : query_res<4>(sh, form);
+  const KernelRes r = query_res(sh, ch, form);
   if (r.measured) cache.emplace(key, r);  // estimates (no device) are not cached
   return r;
 }
 
 }  // namespace
+
+void set_xcd_swizzle(bool on) { g_xcd_swizzle.store(on ? 1 : 0, std::memory_order_relaxed); }
+void set_swar_alt(int mode) { g_alt_mode.store(mode < 0 ? -1 : std::min(mode, 1), std::memory_order_relaxed); }
+void set_prefetch_mode(int mode) { g_pf_mode.store(mode < 0 ? -1 : mode > 0 ? 1 : 0, std::memory_order_relaxed); }
+
+SwarResources swar_resources(SwarShape s, int ch) {
+  const KernelRes r = kernel_res(s, ch, default_form());
+  return SwarResources{r.vgpr, r.lds, r.measured};
+}
 
 // Latency model of one launch on 256 CUs x 4 SIMDs, in gfx950 cycles.
 //   * VALU instructions per wave: steps x per-step row work + load/pack/store
@@ -554,26 +540,12 @@ KernelRes kernel_res(SwarShape sh, int ch, int form) {
 // 4 image sizes, grey/RGB and 1-8-way bands (profiles/r01/band_shape_sweep.txt;
 // tools/fit_swar_data.py + tools/fit_swar_model.py); they pick the measured
 // best shape in 6 of 6 configurations of the current kernel.
-void set_xcd_swizzle(bool on) { g_xcd_swizzle.store(on ? 1 : 0, std::memory_order_relaxed); }
-void set_swar_alt(int mode) { g_alt_mode.store(mode < 0 ? -1 : std::min(mode, 1), std::memory_order_relaxed); }
-void set_prefetch_mode(int mode) { g_pf_mode.store(mode < 0 ? -1 : mode > 0 ? 1 : 0, std::memory_order_relaxed); }
-std::vector<SwarShape> swar_prefetch_shapes() { return std::vector<SwarShape>(std::begin(kPfShapes), std::end(kPfShapes)); }
-
-SwarResources swar_resources(SwarShape s, int ch) {
-  const KernelRes r = kernel_res(s, ch, default_form());
-  return SwarResources{r.vgpr, r.lds, r.measured};
-}
-
 double swar_launch_cycles(SwarShape s, int steps, int ch, int64_t rows, int64_t row_bytes) {
   constexpr double kCyclesMin = 2.88, kCyclesOneWave = 5.86, kStep = 549.0, kRowLoad = 568.0, kLaunch = 17813.0;
   const int np = s.lw;
-  const int hl = (steps * ch + s.lw - 1) / s.lw;
-  if (2 * hl >= 64) return 1e300;
-  const int64_t vbytes = (64 - 2 * hl) * s.lw;
-  const int64_t pairs = (ceil_div<int64_t>(row_bytes, vbytes) + 1) / 2;
-  const int vrows = s.m * s.nw - 2 * steps;
-  if (vrows <= 0 || np < ch) return 1e300;
-  const double g = static_cast<double>(pairs * ceil_div<int64_t>(rows, vrows));
+  const SwarGeom geom = swar_geom(s, ch, steps, rows, row_bytes);
+  if (!geom.ok) return 1e300;
+  const double g = static_cast<double>(geom.tiles);
   const KernelRes res = kernel_res(s, ch, default_form());
   const int vgpr_waves = std::max(1, std::min(8, 512 / round_up(std::max(res.vgpr, 1), 8)));
   const int lds_wgs = res.lds > 0 ? (160 * 1024) / res.lds : 8;
@@ -593,15 +565,13 @@ double swar_launch_cycles(SwarShape s, int steps, int ch, int64_t rows, int64_t 
 
 SwarShape pick_swar_shape(int steps, int ch, int64_t rows, int64_t row_bytes) {
   SwarShape best{0, 0, 0};
-  if (override_shape(best) && best.m * best.nw > 2 * steps && best.lw >= ch &&
-      2 * ((steps * ch + best.lw - 1) / best.lw) < 64)
-    return best;
+  if (override_shape(best) && swar_geom(best, ch, steps, rows, row_bytes).ok) return best;
   double best_cost = 1e300;
-  for (const auto& c : kShapes) {
-    const double cost = swar_launch_cycles(c, steps, ch, rows, row_bytes);
+  for (const auto& t : kTiles) {
+    const double cost = swar_launch_cycles(t.shape, steps, ch, rows, row_bytes);
     if (cost < best_cost) {
       best_cost = cost;
-      best = c;
+      best = t.shape;
     }
   }
   PCONV_CHECK(best.m > 0, "swar temporal kernel: steps too large for every tile shape");
@@ -617,26 +587,26 @@ struct SwarChoice {
 };
 
 void launch_choice(const StencilLaunch& a, Channels ch, hipStream_t stream, SwarChoice c) {
-  if (c.kern == 1) {
-    switch (ch) {
-      case Channels::Grey: launch_pf_ch<1>(a, stream, c.shape, c.form); break;
-      case Channels::Rgb: launch_pf_ch<3>(a, stream, c.shape, c.form); break;
-      case Channels::Rgba: launch_pf_ch<4>(a, stream, c.shape, c.form); break;
-    }
-    return;
-  }
-  switch (ch) {
-    case Channels::Grey: launch_ch<1>(a, stream, c.shape, c.form); break;
-    case Channels::Rgb: launch_ch<3>(a, stream, c.shape, c.form); break;
-    case Channels::Rgba: launch_ch<4>(a, stream, c.shape, c.form); break;
-  }
+  const size_t row = c.kern == 0 || known_pf_shape(c.shape) ? tile_index(c.shape) : kNumTiles;
+  const bool known = with_channels(ch, [&](auto chn) {
+    return with_index<kNumTiles>(row, [&](auto i) {
+      constexpr int CH = decltype(chn)::value;
+      constexpr size_t I = decltype(i)::value;
+      if (c.kern == 0)
+        launch_tile<CH, I, false>(a, stream, c.form);
+      else if constexpr (kTiles[I].pf)
+        launch_tile<CH, I, true>(a, stream, c.form);
+    });
+  });
+  PCONV_CHECK(known, std::string(c.kern == 0 ? "swar temporal kernel" : "swar prefetch kernel") +
+                         ": unsupported tile shape");
 }
 
 // Empirical tuning: the model ranks the shapes, the best few are timed in both
-// step forms on the actual launch (same src -> dst, so the repeats are
-// harmless: every run writes the same bytes) and the fastest (shape, form) is
-// cached per (channels, steps, rows, row bytes).  Never while the stream is
-// being captured into a graph (the engine tunes a step's launches first).
+// step forms on the actual launch (fastest_candidate, tuning.hpp) and the
+// fastest (shape, form) is cached per (channels, steps, rows, row bytes).
+// Never while the stream is being captured into a graph (the engine tunes a
+// step's launches first).
 struct TuneKey {
   int ch, steps;
   int64_t rows, row_bytes;
@@ -646,34 +616,24 @@ struct TuneKey {
 };
 std::mutex g_tune_mu;
 std::map<TuneKey, SwarChoice> g_tuned;
-std::atomic<int> g_autotune{1};
+std::atomic<int> g_shape_tuning{1};     // first-use tuning of both temporal kernels' shapes
 std::atomic<int> g_tune_candidates{6};  // model-ranked shapes timed per launch geometry
-
-bool autotune_enabled() { return g_autotune.load(std::memory_order_relaxed) != 0; }
-
-bool capturing(hipStream_t s) {
-  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-  return hipStreamIsCapturing(s, &st) == hipSuccess && st != hipStreamCaptureStatusNone;
-}
-
-constexpr int kTuneRepeats = 3;
-constexpr int kTunePasses = 2;
 
 SwarChoice tuned_choice(const StencilLaunch& a, Channels ch, hipStream_t stream, bool may_measure) {
   const int c = channel_count(ch);
   const int64_t rows = a.r1 - a.r0;
   const int mode = alt_mode();
+  const auto runs = [&](const SwarShape& sh) { return swar_geom(sh, c, a.steps, rows, a.row_bytes).tiles > 0; };
   SwarChoice fallback;
   fallback.form = default_form();
-  if (pf_mode() == 1 && pf_launch_ok(a, a.steps) && (override_shape(fallback.shape) || !autotune_enabled())) {
+  if (pf_mode() == 1 && pf_launch_ok(a, a.steps) && (override_shape(fallback.shape) || !shape_tuning_enabled())) {
     // forced prefetch kernel, untuned: the overridden shape if it has a
     // prefetch instantiation, else the first prefetch shape that runs
-    if (!override_shape(fallback.shape) || !known_pf_shape(fallback.shape) ||
-        pf_tiles(fallback.shape, c, a.steps, rows, a.row_bytes) == 0) {
+    if (!override_shape(fallback.shape) || !known_pf_shape(fallback.shape) || !runs(fallback.shape)) {
       fallback.shape = SwarShape{0, 0, 0};
-      for (const auto& p : kPfShapes)
-        if (pf_tiles(p, c, a.steps, rows, a.row_bytes) > 0) {
-          fallback.shape = p;
+      for (const auto& t : kTiles)
+        if (t.pf && runs(t.shape)) {
+          fallback.shape = t.shape;
           break;
         }
     }
@@ -684,7 +644,7 @@ SwarChoice tuned_choice(const StencilLaunch& a, Channels ch, hipStream_t stream,
     fallback.shape = pick_swar_shape(a.steps, c, rows, a.row_bytes);
     return fallback;
   }
-  if (override_shape(fallback.shape) || !autotune_enabled()) {
+  if (override_shape(fallback.shape) || !shape_tuning_enabled()) {
     if (!override_shape(fallback.shape)) fallback.shape = pick_swar_shape(a.steps, c, rows, a.row_bytes);
     return fallback;
   }
@@ -699,11 +659,11 @@ SwarChoice tuned_choice(const StencilLaunch& a, Channels ch, hipStream_t stream,
     }
   }
   fallback.shape = pick_swar_shape(a.steps, c, rows, a.row_bytes);
-  if (!may_measure || capturing(stream)) return fallback;
+  if (!may_measure || stream_capturing(stream)) return fallback;
   std::vector<std::pair<double, SwarShape>> ranked;
-  for (const auto& sh : kShapes) {
-    const double cost = swar_launch_cycles(sh, a.steps, c, rows, a.row_bytes);
-    if (cost < 1e299) ranked.emplace_back(cost, sh);
+  for (const auto& t : kTiles) {
+    const double cost = swar_launch_cycles(t.shape, a.steps, c, rows, a.row_bytes);
+    if (cost < 1e299) ranked.emplace_back(cost, t.shape);
   }
   PCONV_CHECK(!ranked.empty(), "swar temporal kernel: steps too large for every tile shape");
   std::sort(ranked.begin(), ranked.end(), [](const auto& x, const auto& y) { return x.first < y.first; });
@@ -729,26 +689,8 @@ SwarChoice tuned_choice(const StencilLaunch& a, Channels ch, hipStream_t stream,
     if (pf_mode() == 1 && !pfs.empty()) cands.clear();  // forced: only these candidates
     cands.insert(cands.end(), pfs.begin(), pfs.end());
   }
-  SwarChoice best = cands.front();
-  if (cands.size() > 1) {
-    // Two interleaved passes, each candidate's best kept: a single pass in a
-    // fixed order mis-ranked large launches (the first candidates ran while
-    // clocks and caches were still settling; 32768^2 grey picked a shape 7 %
-    // slower than the best).
-    Event e0 = Event::create(true), e1 = Event::create(true);
-    std::vector<float> t(cands.size(), 1e30f);
-    for (int pass = 0; pass < kTunePasses; ++pass) {
-      for (size_t i = 0; i < cands.size(); ++i) {
-        if (pass == 0) launch_choice(a, ch, stream, cands[i]);  // warm (code object, caches)
-        e0.record(stream);
-        for (int r = 0; r < kTuneRepeats; ++r) launch_choice(a, ch, stream, cands[i]);
-        e1.record(stream);
-        PCONV_HIP_CHECK(hipEventSynchronize(e1.get()));
-        t[i] = std::min(t[i], Event::elapsed_ms(e0, e1));
-      }
-    }
-    best = cands[std::min_element(t.begin(), t.end()) - t.begin()];
-  }
+  const SwarChoice best = cands[fastest_candidate(
+      cands.size(), stream, [&](size_t i) { launch_choice(a, ch, stream, cands[i]); })];
   std::lock_guard<std::mutex> lk(g_tune_mu);
   g_tuned.emplace(key, best);
   return best;
@@ -756,15 +698,9 @@ SwarChoice tuned_choice(const StencilLaunch& a, Channels ch, hipStream_t stream,
 
 }  // namespace
 
-void set_autotune(bool on) { g_autotune.store(on ? 1 : 0, std::memory_order_relaxed); }
 void set_tune_candidates(int n) { g_tune_candidates.store(std::max(1, n), std::memory_order_relaxed); }
-bool set_shape_tuning(bool on) {
-  const bool prev = autotune_enabled();
-  set_autotune(on);
-  return prev;
-}
-
-bool shape_tuning_enabled() { return autotune_enabled(); }
+bool set_shape_tuning(bool on) { return g_shape_tuning.exchange(on ? 1 : 0, std::memory_order_relaxed) != 0; }
+bool shape_tuning_enabled() { return g_shape_tuning.load(std::memory_order_relaxed) != 0; }
 
 void clear_swar_tuning() {
   {

@@ -393,8 +393,9 @@ PYBIND11_MODULE(_pconv_native, m) {
                               swar_launch_cycles(s, steps, channel_count(parse_channels(ch)), rows, row_bytes));
       },
       py::arg("steps"), py::arg("channels"), py::arg("rows"), py::arg("row_bytes"));
-  m.def("set_autotune", &set_autotune, py::arg("on"),
-        "Time the model's best SWAR tile shapes on first use of a launch geometry (default on).");
+  m.def("set_autotune", &set_shape_tuning, py::arg("on"),
+        "Time the model's best tile shapes on first use of a launch geometry (default on); returns the previous "
+        "setting.");
   m.def("clear_swar_tuning", &clear_swar_tuning);
   m.def("swar_tuned", []() {
     py::list out;
@@ -409,6 +410,11 @@ PYBIND11_MODULE(_pconv_native, m) {
         "How many of the latency model's best SWAR tile shapes the tuner times (default 6).");
   m.def("set_float_shape", &set_float_shape, py::arg("m") = 0, py::arg("nw") = 0,
         "Force the float temporal kernel's tile (m rows per wave, nw waves; m=0: model / tuner).");
+  m.def("float_shapes", []() {
+    py::list out;
+    for (const auto& s : float_shapes()) out.append(py::make_tuple(s.m, s.nw));
+    return out;
+  });
   m.def("swar_prefetch_shapes", []() {
     py::list out;
     for (const auto& s : swar_prefetch_shapes()) out.append(py::make_tuple(s.lw, s.m, s.nw));

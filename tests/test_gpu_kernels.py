@@ -232,6 +232,33 @@ def test_every_swar_shape_bit_exact(native, rng, form):
         native.set_swar_alt(-1)
 
 
+@pytest.mark.parametrize("filt", ["box", "custom"])
+def test_every_float_shape_bit_exact(native, rng, filt):
+    """Force each instantiated tile shape of the float temporal kernel under
+    the zero border, uniform (box) and non-uniform (custom) filter, and compare
+    a fused launch with the CPU fused reference: a 131x167 RGB frame at 4
+    steps (501 row bytes: two column strips, a 5-byte last chunk; two row
+    tiles even for the 16x8 tile), a 131x509 grey frame at 8 steps, and a band
+    of each whose ghost rows reach the image top."""
+    f = _custom_filter(native) if filt == "custom" else filt
+    inputs = [(rng.integers(0, 256, size=(131, 167, 3), dtype=np.uint8), 4),
+              (rng.integers(0, 256, size=(131, 509), dtype=np.uint8), 8)]
+    shapes = native.float_shapes()
+    assert (16, 8) in shapes and (4, 8) in shapes
+    try:
+        for (m, nw) in shapes:
+            native.set_float_shape(m, nw)
+            for img, steps in inputs:
+                if m * nw <= 2 * steps:
+                    continue
+                gpu, cpu = _run_fused(native, img, steps, 0, 131, steps, 0, 131, variant="float_temporal", filt=f)
+                assert np.array_equal(gpu, cpu), (m, nw, img.shape, steps)
+                gpu, cpu = _run_fused(native, img[:40], steps, -5, 45, 16, 30, 200, variant="float_temporal", filt=f)
+                assert np.array_equal(gpu[11:61], cpu[11:61]), (m, nw, img.shape, steps, "band")
+    finally:
+        native.set_float_shape(0, 0)
+
+
 @pytest.mark.parametrize("swizzle", [True, False])
 @pytest.mark.parametrize("form", [0, 1])
 def test_prefetch_kernel_every_shape_bit_exact(native, rng, form, swizzle):
