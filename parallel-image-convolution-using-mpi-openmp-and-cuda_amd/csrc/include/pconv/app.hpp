@@ -41,6 +41,12 @@ struct AppReport {
   int cpu_reps = -1, gpu_reps = -1;
   double cpu_rep_s = 0;
   std::string auto_choice;
+  // --converge-every: repetitions actually run (-1: the flag was not given),
+  // whether the result is a fixed point, and the last check's count of bytes
+  // one more repetition would change.
+  int reps_done = -1;
+  bool converged = false;
+  uint64_t residual = 0;
 };
 
 // Runs the CLI (argv as given).  Returns the process exit code.

@@ -46,6 +46,9 @@ struct CliConfig {
   int threads = 0;
   TimeFormat format = TimeFormat::Auto;
   int checkpoint_every = 0;
+  // --converge-every K: a residual check every K repetitions; the run stops at
+  // the first fixed point and `reps` is the maximum.  0 = off.
+  int converge_every = 0;
   bool explain = false;
   double timeout_s = 600.0;
   bool quiet = false;

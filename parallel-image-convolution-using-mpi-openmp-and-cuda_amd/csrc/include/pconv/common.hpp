@@ -35,6 +35,15 @@ enum class Border : int { Zero = 0, Replicate = 1 };
 const char* border_name(Border b);
 Border parse_border(const std::string& s);  // "zero" | "replicate"
 
+// Outcome of a run that stops at the map's fixed point (`residual` = bytes one
+// more repetition would change, counted over the whole image; 0 = converged).
+struct StableStats {
+  int reps_done = 0;      // repetitions actually run
+  bool converged = false; // the returned image is a fixed point
+  uint64_t residual = 0;  // the last check's count: it describes the returned image
+  int checks = 0;         // residual checks made
+};
+
 // Thrown by every layer.  `what()` carries "[rank R] where: message".
 class Error : public std::runtime_error {
  public:

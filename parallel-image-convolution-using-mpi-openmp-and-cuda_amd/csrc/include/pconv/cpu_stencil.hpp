@@ -50,6 +50,26 @@ void cpu_fused_launch(const Filter& f, Channels ch, const FrameLayout& lay, cons
 void cpu_convolve(const Filter& f, const ImageGeom& geom, const uint8_t* in, uint8_t* out,
                   int reps, CpuBackend be, int threads = 0, Border border = Border::Zero);
 
+// Residual of the iterated map (the CPU twin of launch_residual): the number
+// of bytes in rows [r0, r1) of the frame that one more repetition would
+// change.  cpu_step's row kernels into a scratch row, compared and counted —
+// no second frame.  Rows outside the global image [0, height) read as zeros
+// (Border::Zero, whatever the frame holds there) or clamp (Border::Replicate);
+// [r0, r1) is clipped to the image.  height < 0: the owned rows end the image.
+uint64_t cpu_residual(const Filter& f, Channels ch, const FrameLayout& lay, const uint8_t* src_frame, int64_t r0,
+                      int64_t r1, CpuBackend be, Border border = Border::Zero, int64_t g_row0 = 0,
+                      int64_t height = -1);
+// The same for a contiguous image (pitch == row_bytes).
+uint64_t cpu_image_residual(const Filter& f, const ImageGeom& geom, const uint8_t* in, CpuBackend be, int threads = 0,
+                            Border border = Border::Zero);
+
+// cpu_convolve that stops at the fixed point: chunks of `check_every`
+// repetitions (the last one shorter), a residual check after each chunk, at
+// most max_reps repetitions; the final check is made even at max_reps.
+StableStats cpu_convolve_until_stable(const Filter& f, const ImageGeom& geom, const uint8_t* in, uint8_t* out,
+                                      int max_reps, int check_every, CpuBackend be, int threads = 0,
+                                      Border border = Border::Zero);
+
 // OpenMP team size when the user set none (OMP_NUM_THREADS unset, no
 // --threads): the CPUs this process may run on (affinity mask), capped by the
 // cgroup CPU quota (a container or GPU-box slice sees every CPU of the

@@ -16,6 +16,7 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include <functional>
 #include <map>
 #include <memory>
 #include <tuple>
@@ -192,6 +193,26 @@ class BandEngine {
 
   // Enqueue `reps` repetitions (async).  stats filled after synchronize().
   void run(int reps);
+  // Residual of the current source frame (kernels.hpp launch_residual): the
+  // bytes of this band's owned rows that one more repetition would change.
+  // Collective over the bands of an image: a band with neighbours whose ghost
+  // rows are not valid first fills its whole ghost zone (exchange_now), which
+  // the next run() then plans as pre-loaded — in steady state a check adds no
+  // exchange.  Launched on the compute stream, never captured into a graph;
+  // synchronises and returns this band's count.
+  uint64_t residual();
+  // Run to the fixed point: chunks of `check_every` repetitions (the last one
+  // shorter), residual() after each, at most max_reps repetitions; the final
+  // check is made even at max_reps, so the result describes the frame.  A
+  // band with neighbours passes `reduce`: local count -> sum over the ranks
+  // (every rank then takes the same decision).  `poll` (optional) runs after
+  // each chunk is enqueued and after each exchange of a check, before the
+  // engine synchronises: a transport's watchdog / error poll.
+  // last_stats() afterwards: launches / exchanges / loop_ms summed over the chunks.
+  StableStats run_until_stable(int max_reps, int check_every,
+                               const std::function<uint64_t(uint64_t)>& reduce = nullptr,
+                               const std::function<void()>& poll = nullptr);
+
   // One whole serving step — H2D of host rows [in_r0, in_r1) (ghost rows
   // allowed), `reps` repetitions, D2H of the owned rows — as ONE cached
   // hipGraph launched on the compute stream: one host API call per image
@@ -237,6 +258,15 @@ class BandEngine {
   StencilLaunch make_launch(const LaunchSpec& l, int cur) const;
   // Settle per-launch choices (tile-shape tuning) of a plan before capturing it.
   void prepare(const std::vector<Phase>& ph);
+  // residual(): fill the ghost zone of a band with neighbours unless it is
+  // valid (true: an exchange was enqueued).
+  bool refresh_halo();
+  // A check in two halves, so that a chunk can be enqueued between them:
+  // exchange (if needed) + residual launch + read-back of the running count
+  // on the compute stream; then wait for the read-back and return this
+  // check's count.  One check is outstanding at a time.
+  void enqueue_residual();
+  uint64_t finish_residual();
 
   ImageGeom geom_;
   Band band_;
@@ -247,6 +277,10 @@ class BandEngine {
   int cur_ = 0;
   bool halo_valid_ = false;
   int pre_exchanges_ = 0;  // exchange_now() calls since the last run()
+  DeviceBuffer res_count_;            // residual(): the 64-bit device counter (allocated on first use)
+  PinnedBuffer res_host_;             // pinned word the running count is read back into
+  Event res_ev_;                      // the latest read-back has landed
+  uint64_t res_seen_ = 0;             // the running count at the latest check read
   Stream own_cs_, own_ms_;
   hipStream_t cs_ = nullptr, ms_ = nullptr;
   Event ev_ready_, ev_halo_, ev_t0_, ev_t1_, ev_sync_;
@@ -263,6 +297,10 @@ class BandEngine {
   // recorded).
   void set_stream_trace(bool on) { stream_trace_ = on; }
   std::vector<std::vector<double>> stream_trace();
+  // Diagnostics: `launches` residual launches on the current frame, each
+  // between two timing events on the compute stream (the counter's zeroing
+  // and read-back are outside them); ms per launch.
+  std::vector<double> time_residual(int launches);
   // Create the streamed-image events for `chunks` chunks now (set-up), not
   // inside the first streamed image this engine runs.
   void reserve_stream_events(size_t chunks) {

@@ -76,6 +76,18 @@ void launch_float_temporal(const Filter& f, Channels ch, const StencilLaunch& a,
 // graph capture).
 void prepare_float_temporal(const Filter& f, Channels ch, const StencilLaunch& a, hipStream_t stream);
 
+// Residual of the iterated map at the frame `a.src` (kernels/residual.hip):
+// one repetition of `f` under `a.border` is evaluated in registers for rows
+// [a.r0, a.r1) and the bytes of [0, row_bytes) with step(x) != x are counted.
+// Nothing is stored but the count, ADDED to *counter (device memory, zeroed by
+// the caller): zero means the rows are a fixed point of the repetition.  Reads
+// src, pitch, row_bytes, r0, r1, frame_lo, frame_hi, g_row0, height and border
+// (dst and steps are ignored); the rows are clipped to the global image and
+// validated against the frame like a one-step launch_stencil.
+void launch_residual(const Filter& f, Channels ch, const StencilLaunch& a, uint64_t* counter, hipStream_t stream);
+// Rows one workgroup of the residual kernel covers (tests place image heights around it).
+constexpr int kResidualBlockRows = 32;
+
 // Whether `v` (or Auto) can fuse `steps` > 1 for this filter.
 bool supports_fusion(const Filter& f, KernelVariant v);
 

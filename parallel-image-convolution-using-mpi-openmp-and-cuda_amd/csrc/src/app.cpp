@@ -79,11 +79,12 @@ EngineOptions engine_options(const CliConfig& c, const ImageGeom& g, int world, 
   return o;
 }
 
-int64_t compare_with_oracle(const CliConfig& c, const ImageGeom& g, const uint8_t* result) {
+// reps < 0: the requested repetitions (--converge-every passes the ones actually run)
+int64_t compare_with_oracle(const CliConfig& c, const ImageGeom& g, const uint8_t* result, int reps = -1) {
   std::vector<uint8_t> in(static_cast<size_t>(g.bytes())), ref(static_cast<size_t>(g.bytes()));
   load_rows(c, g, 0, g.height, in.data(), g.row_bytes());
-  cpu_convolve(Filter::by_name(c.filter), g, in.data(), ref.data(), c.reps, CpuBackend::OpenMP, c.threads,
-               c.border);
+  cpu_convolve(Filter::by_name(c.filter), g, in.data(), ref.data(), reps < 0 ? c.reps : reps, CpuBackend::OpenMP,
+               c.threads, c.border);
   int64_t bad = 0;
   for (size_t i = 0; i < ref.size(); ++i) bad += ref[i] != result[i];
   return bad;
@@ -129,12 +130,24 @@ AppReport run_cpu(const CliConfig& c) {
       copy_out();
       write_image(out_path(c) + ".rep" + std::to_string(done), g, img.data());
     }
+    // --converge-every K: the residual of the newest frame every K
+    // repetitions and after the last one; the loop ends at the first zero.
+    if (c.converge_every > 0 && (done % c.converge_every == 0 || done == c.reps)) {
+      r.residual = cpu_residual(f, g.channels, lay, src, 0, g.height, be, c.border, 0, g.height);
+      r.reps_done = done;
+      if (r.residual == 0) break;
+    }
   }
+  if (c.converge_every > 0 && r.reps_done < 0) {  // (repetitions 0: the input itself is checked)
+    r.residual = cpu_residual(f, g.channels, lay, src, 0, g.height, be, c.border, 0, g.height);
+    r.reps_done = 0;
+  }
+  r.converged = c.converge_every > 0 && r.residual == 0;
   r.loop_s = wall_seconds() - l0;
   copy_out();
   r.output = out_path(c);
   write_image(r.output, g, img.data());
-  if (c.check) r.mismatches = compare_with_oracle(c, g, img.data());
+  if (c.check) r.mismatches = compare_with_oracle(c, g, img.data(), r.reps_done);
   r.e2e_s = wall_seconds() - t0;
   return r;
 }
@@ -342,6 +355,15 @@ AppReport run_gpu1(const CliConfig& c, JobCache* cache) {
   const double l0 = wall_seconds();
   int done = 0;
   const int chunk = c.checkpoint_every > 0 ? c.checkpoint_every : std::max(1, c.reps);
+  if (c.converge_every > 0) {
+    // chunks of K repetitions as above, a residual launch between them
+    const StableStats st = eng.run_until_stable(c.reps, c.converge_every);
+    r.launches = eng.last_stats().launches;
+    r.reps_done = st.reps_done;
+    r.converged = st.converged;
+    r.residual = st.residual;
+    done = c.reps;
+  }
   while (done < c.reps) {
     const int k = std::min(chunk, c.reps - done);
     eng.run(k);
@@ -386,7 +408,7 @@ AppReport run_gpu1(const CliConfig& c, JobCache* cache) {
   r.fuse = eng.options().fuse;
   r.kernel = kernel_variant_name(eng.options().variant);
   r.copies = eng.options().kernel_copies ? "kernel" : "sdma";
-  if (c.check) r.mismatches = compare_with_oracle(c, g, host);
+  if (c.check) r.mismatches = compare_with_oracle(c, g, host, r.reps_done);
   r.since_exec_s = seconds_since_exec();
   return r;
 }
@@ -547,6 +569,11 @@ struct SharedState {
   double loop_s[kMaxRanks];
   int launches[kMaxRanks];
   int exchanges[kMaxRanks];
+  // --converge-every: every rank's residual count of the latest check (summed
+  // by every rank between two barriers) and rank 0's outcome
+  uint64_t residual[kMaxRanks];
+  int reps_done, converged;
+  uint64_t residual_sum;
   char error[512];
   // --transport ipc: every rank's frame handles (hipIpcMemHandle_t x 2) and
   // the flag segment's name
@@ -692,7 +719,36 @@ void run_rank(const CliConfig& c, SharedState* sh, uint8_t* halo_slots, int64_t 
   // (run() invalidates the pre-loaded ones).
   const int chunk = c.checkpoint_every > 0 ? c.checkpoint_every : std::max(1, c.reps);
   int done = 0, launches = 0, exchanges = 0;
-  do {
+  if (c.converge_every > 0) {
+    // Chunks of K repetitions with a residual check after each: every rank
+    // publishes its count, all meet, every rank sums the counts and so takes
+    // the same decision (the reference family's MPI_Allreduce); the second
+    // barrier keeps the next check's counts apart.
+    auto reduce = [&](uint64_t local) {
+      sh->residual[rank] = local;
+      shm_barrier(sh, world, c.timeout_s);
+      uint64_t sum = 0;
+      for (int i = 0; i < world; ++i) sum += sh->residual[i];
+      shm_barrier(sh, world, c.timeout_s);
+      return sum;
+    };
+    auto poll = [&] {
+      if (comm) {
+        comm->wait(eng.compute_stream(), c.timeout_s);
+        comm->wait(eng.comm_stream(), c.timeout_s);
+      }
+    };
+    const StableStats st = eng.run_until_stable(c.reps, c.converge_every, reduce, poll);
+    if (ipct) ipct->check();
+    launches = eng.last_stats().launches;
+    exchanges = eng.last_stats().exchanges;
+    if (rank == 0) {
+      sh->reps_done = st.reps_done;
+      sh->converged = st.converged ? 1 : 0;
+      sh->residual_sum = st.residual;
+    }
+    done = c.reps;
+  } else do {
     const int k = std::min(chunk, c.reps - done);
     eng.run(k);
     if (comm) {
@@ -799,6 +855,11 @@ AppReport run_multi(const CliConfig& c) {
     r.launches = std::max(r.launches, sh->launches[i]);
     r.exchanges = std::max(r.exchanges, sh->exchanges[i]);
   }
+  if (c.converge_every > 0) {
+    r.reps_done = sh->reps_done;
+    r.converged = sh->converged != 0;
+    r.residual = sh->residual_sum;
+  }
   munmap(mem, sizeof(SharedState));
   const EngineOptions o = engine_options(c, g, c.gpus, 0);
   r.halo = o.halo_depth;
@@ -807,7 +868,7 @@ AppReport run_multi(const CliConfig& c) {
   if (c.check) {
     std::vector<uint8_t> out(static_cast<size_t>(g.bytes()));
     read_image(r.output, g, out.data());
-    r.mismatches = compare_with_oracle(c, g, out.data());
+    r.mismatches = compare_with_oracle(c, g, out.data(), r.reps_done);
   }
   r.e2e_s = wall_seconds() - t0;
   return r;
@@ -1063,13 +1124,13 @@ std::string run_bench(const CliConfig& c) { return run_bench_impl(c); }
 
 AppReport run_app(const CliConfig& c, JobCache* cache) {
   AppReport r;
-  if (c.backend == Backend::Auto && cache == nullptr && c.checkpoint_every == 0) {
+  if (c.backend == Backend::Auto && cache == nullptr && c.checkpoint_every == 0 && c.converge_every == 0) {
     r = run_auto(c);  // sets r.gpus (0 when the GPU was not used)
   } else if (c.backend == Backend::Cpu || c.backend == Backend::Omp) {
     r = run_cpu(c);
     r.gpus = 0;
   } else if (c.gpus > 1) {
-    // (--backend auto in a resident server or with checkpoints: the GPU path)
+    // (--backend auto in a resident server, with checkpoints or with --converge-every: the GPU path)
     PCONV_CHECK(cache == nullptr, "the resident service runs one GPU per server (--gpus 1)");
     r = run_multi(c);
     r.gpus = c.gpus;
@@ -1077,14 +1138,15 @@ AppReport run_app(const CliConfig& c, JobCache* cache) {
     r = run_gpu1(c, cache);
     r.gpus = c.gpus;
   }
-  const double px = static_cast<double>(c.width) * static_cast<double>(c.height) * c.reps;
+  const double px = static_cast<double>(c.width) * static_cast<double>(c.height) * (r.reps_done >= 0 ? r.reps_done : c.reps);
   r.mpix_per_s = r.loop_s > 0 ? px / r.loop_s / 1e6 : 0.0;
   return r;
 }
 
 std::string report_json(const CliConfig& c, const AppReport& r) {
   std::ostringstream os;
-  const double px = static_cast<double>(c.width) * static_cast<double>(c.height) * c.reps;
+  const double px =
+      static_cast<double>(c.width) * static_cast<double>(c.height) * (r.reps_done >= 0 ? r.reps_done : c.reps);
   os << "{\"width\": " << c.width << ", \"height\": " << c.height << ", \"channels\": \""
      << channels_name(c.channels) << "\", \"reps\": " << c.reps << ", \"filter\": \"" << c.filter
      << "\", \"border\": \"" << border_name(c.border) << "\", \"backend\": \""
@@ -1105,6 +1167,9 @@ std::string report_json(const CliConfig& c, const AppReport& r) {
     os << ", \"hip_runtime_version\": " << h.runtime_version << ", \"hip_runtime_path\": \""
        << json_escape(h.runtime_path) << "\"";
   }
+  if (r.reps_done >= 0)
+    os << ", \"reps_done\": " << r.reps_done << ", \"converged\": " << (r.converged ? "true" : "false")
+       << ", \"residual\": " << r.residual;
   if (!r.copies.empty()) os << ", \"copies\": \"" << r.copies << "\"";
   if (!r.phases.empty()) {
     os << ", \"phases_s\": {";
@@ -1248,6 +1313,13 @@ int conv_main(int argc, char** argv) {
       if (fmt == TimeFormat::Cuda || fmt == TimeFormat::Both) std::printf("Execution time: %.3f sec\n", r.e2e_s);
     }
     if (c.json) std::printf("%s\n", report_json(c, r).c_str());
+    if (r.reps_done >= 0 && !c.quiet) {
+      if (r.converged)
+        std::fprintf(stderr, "fixed point after %d repetitions\n", r.reps_done);
+      else
+        std::fprintf(stderr, "no fixed point within %d repetitions (%" PRIu64 " bytes still change)\n", r.reps_done,
+                     r.residual);
+    }
     if (c.check) {
       std::fprintf(stderr, "check: %" PRId64 " mismatching bytes vs CPU oracle\n", r.mismatches);
       if (r.mismatches != 0) return 2;

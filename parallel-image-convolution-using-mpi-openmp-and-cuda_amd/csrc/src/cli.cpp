@@ -52,6 +52,9 @@ std::string help_text(const std::string& prog) {
          "  --threads N               OpenMP threads for --backend omp\n"
          "  --format {cuda,mpi,both}  timing line(s) to print (default: cuda for 1 GPU, mpi otherwise)\n"
          "  --checkpoint-every K      write <out>.rep<N> every K repetitions\n"
+         "  --converge-every K        stop at the fixed point: every K repetitions count the bytes one more\n"
+         "                            repetition would change and end the run at zero (`repetitions` becomes\n"
+         "                            the maximum; not with --checkpoint-every)\n"
          "  --explain                 print the halo/launch schedule\n"
          "  --timeout S               RCCL watchdog timeout in seconds (default 600)\n"
          "  --transport {rccl,shm,ipc}  multi-GPU halo transport (shm: host-staged through shared memory;\n"
@@ -158,6 +161,8 @@ CliConfig parse_cli(const std::vector<std::string>& args) {
       else PCONV_FAIL("invalid --format '" + v + "' (cuda|mpi|both)");
     } else if (a == "--checkpoint-every") {
       c.checkpoint_every = static_cast<int>(parse_int(next("--checkpoint-every"), "--checkpoint-every", 1, INT_MAX));
+    } else if (a == "--converge-every") {
+      c.converge_every = static_cast<int>(parse_int(next("--converge-every"), "--converge-every", 1, INT_MAX));
     } else if (a == "--explain") {
       c.explain = true;
     } else if (a == "--timeout") {
@@ -224,6 +229,9 @@ CliConfig parse_cli(const std::vector<std::string>& args) {
     }
   }
   if (c.backend != Backend::Hip && c.gpus != 1) PCONV_FAIL("--gpus requires --backend hip");
+  if (c.converge_every > 0 && c.checkpoint_every > 0)
+    PCONV_FAIL("--converge-every cannot be combined with --checkpoint-every");
+  if (c.converge_every > 0 && c.bench_steps > 0) PCONV_FAIL("--converge-every cannot be combined with --bench");
   if (c.backend == Backend::Auto && c.bench_steps > 0) PCONV_FAIL("--bench runs on the GPU (--backend hip)");
   if (c.emulate_world > 0 && (c.bench_steps == 0 || c.gpus != 1))
     PCONV_FAIL("--emulate needs --bench and --gpus 1 (one process times one rank of the split)");

@@ -146,6 +146,37 @@ const uint8_t* edge_padded(const uint8_t* p, int64_t n, uint8_t* buf) {
   return buf + CH;
 }
 
+// One output row from its three input rows (column -CH .. n + CH readable).
+template <int CH>
+void eval_row(const Filter& f, const uint8_t* a, const uint8_t* b, const uint8_t* c, uint8_t* o, int64_t n) {
+  if (f.binomial121)
+    row_binomial<CH>(a, b, c, o, n);
+  else if (f.int_exact)
+    row_int<CH>(f, a, b, c, o, n);
+  else
+    row_float<CH>(f, a, b, c, o, n);
+}
+
+// Replicate border, frame row r: the three input rows with the taps clamped
+// to the GLOBAL image — the row above global row 0 is row 0, the row below
+// the last is the last; columns through padded copies, so the same row
+// kernels (integer / float, baseline / AVX2) serve.
+template <int CH>
+void replicate_rows(const FrameLayout& lay, const uint8_t* src, int64_t r, int64_t g_row0, int64_t height,
+                    const uint8_t*& a, const uint8_t*& b, const uint8_t*& c) {
+  const int64_t n = lay.row_bytes;
+  thread_local std::vector<uint8_t> rows3;
+  const size_t w = static_cast<size_t>(n + 2 * CH);
+  if (rows3.size() < 3 * w) rows3.resize(3 * w);
+  const int64_t g = g_row0 + r;
+  const uint8_t* pb = src + lay.offset(r);
+  const uint8_t* pa = g - 1 >= 0 ? src + lay.offset(r - 1) : pb;
+  const uint8_t* pc = g + 1 < height ? src + lay.offset(r + 1) : pb;
+  a = edge_padded<CH>(pa, n, rows3.data());
+  c = edge_padded<CH>(pc, n, rows3.data() + 2 * w);
+  b = edge_padded<CH>(pb, n, rows3.data() + w);
+}
+
 template <int CH>
 void step_rows(const Filter& f, const FrameLayout& lay, const uint8_t* src, uint8_t* dst, int64_t r0, int64_t r1,
                CpuBackend be, Border border, int64_t g_row0, int64_t height) {
@@ -155,26 +186,8 @@ void step_rows(const Filter& f, const FrameLayout& lay, const uint8_t* src, uint
     const uint8_t* b = src + lay.offset(r);
     const uint8_t* c = src + lay.offset(r + 1);
     uint8_t* o = dst + lay.offset(r);
-    if (border == Border::Replicate) {
-      // Taps clamp to the GLOBAL image: the row above global row 0 is row 0,
-      // the row below the last is the last; columns through padded copies, so
-      // the same row kernels (integer / float, baseline / AVX2) serve.
-      thread_local std::vector<uint8_t> rows3;
-      const size_t w = static_cast<size_t>(n + 2 * CH);
-      if (rows3.size() < 3 * w) rows3.resize(3 * w);
-      const int64_t g = g_row0 + r;
-      const uint8_t* pa = g - 1 >= 0 ? a : b;
-      const uint8_t* pc = g + 1 < height ? c : b;
-      a = edge_padded<CH>(pa, n, rows3.data());
-      c = edge_padded<CH>(pc, n, rows3.data() + 2 * w);
-      b = edge_padded<CH>(b, n, rows3.data() + w);
-    }
-    if (f.binomial121)
-      row_binomial<CH>(a, b, c, o, n);
-    else if (f.int_exact)
-      row_int<CH>(f, a, b, c, o, n);
-    else
-      row_float<CH>(f, a, b, c, o, n);
+    if (border == Border::Replicate) replicate_rows<CH>(lay, src, r, g_row0, height, a, b, c);
+    eval_row<CH>(f, a, b, c, o, n);
   };
   if (be == CpuBackend::OpenMP) {
     // Below ~32 KiB of output a step is a few microseconds on one core: the
@@ -188,7 +201,62 @@ void step_rows(const Filter& f, const FrameLayout& lay, const uint8_t* src, uint
   }
 }
 
+// step_rows' evaluation into a scratch row, compared with the source row and
+// counted.  Zero border: a row outside the global image is a row of zeros,
+// whatever the frame holds there.
+template <int CH>
+uint64_t residual_rows(const Filter& f, const FrameLayout& lay, const uint8_t* src, int64_t r0, int64_t r1,
+                       CpuBackend be, Border border, int64_t g_row0, int64_t height) {
+  const int64_t n = lay.row_bytes;
+  auto body = [&](int64_t r) -> uint64_t {
+    thread_local std::vector<uint8_t> scratch, zeros;
+    if (scratch.size() < static_cast<size_t>(n)) scratch.resize(static_cast<size_t>(n));
+    const uint8_t* a = src + lay.offset(r - 1);
+    const uint8_t* b = src + lay.offset(r);
+    const uint8_t* c = src + lay.offset(r + 1);
+    if (border == Border::Replicate) {
+      replicate_rows<CH>(lay, src, r, g_row0, height, a, b, c);
+    } else {
+      const int64_t g = g_row0 + r;
+      if (g - 1 < 0 || g + 1 >= height) {
+        if (zeros.size() < static_cast<size_t>(n + 2 * CH)) zeros.assign(static_cast<size_t>(n + 2 * CH), 0);
+        if (g - 1 < 0) a = zeros.data() + CH;
+        if (g + 1 >= height) c = zeros.data() + CH;
+      }
+    }
+    uint8_t* o = scratch.data();
+    eval_row<CH>(f, a, b, c, o, n);
+    uint64_t cnt = 0;
+    for (int64_t x = 0; x < n; ++x) cnt += o[x] != b[x];
+    return cnt;
+  };
+  uint64_t total = 0;
+  if (be == CpuBackend::OpenMP) {
+    const bool team = (r1 - r0) * n >= (int64_t{32} << 10);  // as in step_rows
+#pragma omp parallel for schedule(static) reduction(+ : total) if (team)
+    for (int64_t r = r0; r < r1; ++r) total += body(r);
+  } else {
+    for (int64_t r = r0; r < r1; ++r) total += body(r);
+  }
+  return total;
+}
+
 }  // namespace
+
+uint64_t cpu_residual(const Filter& f, Channels ch, const FrameLayout& lay, const uint8_t* src_frame, int64_t r0,
+                      int64_t r1, CpuBackend be, Border border, int64_t g_row0, int64_t height) {
+  if (height < 0) height = g_row0 + lay.rows;  // the frame's owned rows end the image
+  r0 = std::max(r0, -g_row0);
+  r1 = std::min(r1, height - g_row0);
+  if (r1 <= r0) return 0;
+  PCONV_CHECK(r0 >= -lay.halo + 1 && r1 <= lay.rows + lay.halo - 1, "cpu_residual: rows out of frame");
+  switch (ch) {
+    case Channels::Grey: return residual_rows<1>(f, lay, src_frame, r0, r1, be, border, g_row0, height);
+    case Channels::Rgb: return residual_rows<3>(f, lay, src_frame, r0, r1, be, border, g_row0, height);
+    case Channels::Rgba: return residual_rows<4>(f, lay, src_frame, r0, r1, be, border, g_row0, height);
+  }
+  return 0;
+}
 
 void cpu_step(const Filter& f, Channels ch, const FrameLayout& lay, const uint8_t* src_frame, uint8_t* dst_frame,
               int64_t r0, int64_t r1, CpuBackend be, Border border, int64_t g_row0, int64_t height) {
@@ -300,6 +368,63 @@ void cpu_convolve(const Filter& f, const ImageGeom& geom, const uint8_t* in, uin
   }
   if (be == CpuBackend::OpenMP && threads > 0) omp_set_num_threads(saved);
   for (int64_t r = 0; r < geom.height; ++r) std::memcpy(out + r * rb, src + lay.offset(r), rb);
+}
+
+namespace {
+
+// OpenMP team of a whole-image call (cpu_convolve's rule), restored on exit.
+struct TeamScope {
+  int saved = omp_get_max_threads();
+  bool set = false;
+  TeamScope(CpuBackend be, int threads) {
+    if (be == CpuBackend::OpenMP && threads <= 0 && !std::getenv("OMP_NUM_THREADS")) threads = default_cpu_threads();
+    set = be == CpuBackend::OpenMP && threads > 0;
+    if (set) omp_set_num_threads(threads);
+  }
+  ~TeamScope() {
+    if (set) omp_set_num_threads(saved);
+  }
+};
+
+}  // namespace
+
+uint64_t cpu_image_residual(const Filter& f, const ImageGeom& geom, const uint8_t* in, CpuBackend be, int threads,
+                            Border border) {
+  geom.validate();
+  const int64_t rb = geom.row_bytes();
+  const FrameLayout lay = FrameLayout::make(rb, geom.height, 1);
+  std::vector<uint8_t> fa(static_cast<size_t>(lay.bytes()), 0);
+  for (int64_t r = 0; r < geom.height; ++r) std::memcpy(fa.data() + lay.offset(r), in + r * rb, rb);
+  TeamScope team(be, threads);
+  return cpu_residual(f, geom.channels, lay, fa.data(), 0, geom.height, be, border, 0, geom.height);
+}
+
+StableStats cpu_convolve_until_stable(const Filter& f, const ImageGeom& geom, const uint8_t* in, uint8_t* out,
+                                      int max_reps, int check_every, CpuBackend be, int threads, Border border) {
+  geom.validate();
+  PCONV_CHECK(max_reps >= 0, "repetitions must be >= 0");
+  PCONV_CHECK(check_every >= 1, "check_every must be >= 1");
+  const int64_t rb = geom.row_bytes();
+  const FrameLayout lay = FrameLayout::make(rb, geom.height, 1);
+  std::vector<uint8_t> fa(static_cast<size_t>(lay.bytes()), 0), fb(static_cast<size_t>(lay.bytes()), 0);
+  for (int64_t r = 0; r < geom.height; ++r) std::memcpy(fa.data() + lay.offset(r), in + r * rb, rb);
+  TeamScope team(be, threads);
+  uint8_t* src = fa.data();
+  uint8_t* dst = fb.data();
+  StableStats st;
+  do {
+    const int k = std::min(check_every, max_reps - st.reps_done);
+    for (int t = 0; t < k; ++t) {
+      cpu_step(f, geom.channels, lay, src, dst, 0, geom.height, be, border, 0, geom.height);
+      std::swap(src, dst);
+    }
+    st.reps_done += k;
+    st.residual = cpu_residual(f, geom.channels, lay, src, 0, geom.height, be, border, 0, geom.height);
+    ++st.checks;
+    st.converged = st.residual == 0;
+  } while (!st.converged && st.reps_done < max_reps);
+  for (int64_t r = 0; r < geom.height; ++r) std::memcpy(out + r * rb, src + lay.offset(r), rb);
+  return st;
 }
 
 }  // namespace pconv

@@ -335,6 +335,132 @@ void BandEngine::run(int reps) {
   halo_valid_ = false;
 }
 
+bool BandEngine::refresh_halo() {
+  if ((band_.up < 0 && band_.down < 0) || halo_valid_) return false;
+  // The rows next to a band edge read the neighbours' newest rows: the whole
+  // ghost zone now, after this band's launches and before the next ones, so
+  // that the next run() finds it pre-loaded.
+  const bool split = ms_ != cs_;
+  if (split) {
+    ev_ready_.record(cs_);
+    ev_ready_.wait_on(ms_);
+  }
+  exchange_now();
+  if (split) {
+    ev_halo_.record(ms_);
+    ev_halo_.wait_on(cs_);
+  }
+  return true;
+}
+
+void BandEngine::enqueue_residual() {
+  TraceRange tr("pconv.residual");
+  if (!res_count_.data()) {
+    // (a one-shot process keeps off SDMA and the runtime's blit programs here too)
+    res_count_ = DeviceBuffer(16);
+    res_host_ = PinnedBuffer(16);
+    if (opt_.kernel_copies)
+      launch_fill_zero(res_count_.data(), 16, cs_);
+    else
+      PCONV_HIP_CHECK(hipMemsetAsync(res_count_.data(), 0, 16, cs_));
+    res_ev_ = Event::create();
+  }
+  refresh_halo();
+  StencilLaunch a = make_launch(LaunchSpec{}, cur_);
+  a.r0 = 0;
+  a.r1 = band_.rows;
+  // The device counter is never zeroed again: it runs on, a check is the
+  // difference to the value the check before it read (the stream is in order).
+  launch_residual(filter_, geom_.channels, a, reinterpret_cast<uint64_t*>(res_count_.data()), cs_);
+  if (opt_.kernel_copies)
+    launch_copy_rows(res_count_.data(), 16, res_host_.data(), 16, 16, 1, cs_);
+  else
+    PCONV_HIP_CHECK(hipMemcpyAsync(res_host_.data(), res_count_.data(), 16, hipMemcpyDeviceToHost, cs_));
+  res_ev_.record(cs_);
+}
+
+uint64_t BandEngine::finish_residual() {
+  res_ev_.sync();
+  uint64_t total = 0;
+  std::memcpy(&total, res_host_.data(), sizeof(total));
+  const uint64_t n = total - res_seen_;
+  res_seen_ = total;
+  return n;
+}
+
+uint64_t BandEngine::residual() {
+  enqueue_residual();
+  const uint64_t n = finish_residual();
+  synchronize();
+  return n;
+}
+
+std::vector<double> BandEngine::time_residual(int launches) {
+  (void)residual();  // the counter exists, the ghost zone is valid
+  StencilLaunch a = make_launch(LaunchSpec{}, cur_);
+  a.r0 = 0;
+  a.r1 = band_.rows;
+  std::vector<double> ms;
+  for (int i = 0; i < launches; ++i) {
+    ev_t0_.record(cs_);
+    launch_residual(filter_, geom_.channels, a, reinterpret_cast<uint64_t*>(res_count_.data()), cs_);
+    ev_t1_.record(cs_);
+    PCONV_HIP_CHECK(hipStreamSynchronize(cs_));
+    ms.push_back(Event::elapsed_ms(ev_t0_, ev_t1_));
+  }
+  (void)residual();  // (the next check's difference starts behind these launches)
+  return ms;
+}
+
+StableStats BandEngine::run_until_stable(int max_reps, int check_every,
+                                         const std::function<uint64_t(uint64_t)>& reduce,
+                                         const std::function<void()>& poll) {
+  PCONV_CHECK(max_reps >= 0, "repetitions must be >= 0");
+  PCONV_CHECK(check_every >= 1, "check_every must be >= 1");
+  PCONV_CHECK(reduce || (band_.up < 0 && band_.down < 0),
+              "run_until_stable: a band with neighbours needs the sum of the ranks' counts");
+  StableStats st;
+  RunStats sum;
+  const double w0 = wall_seconds();
+  auto chunk = [&](int k) {
+    run(k);
+    if (poll) poll();
+    sum.launches += stats_.launches;
+    sum.exchanges += stats_.exchanges;
+  };
+  auto check = [&] {
+    enqueue_residual();
+    if (poll) poll();  // (the check's exchange, polled like a chunk's)
+  };
+  int done = std::min(check_every, max_reps);
+  chunk(done);
+  check();
+  for (;;) {
+    // The next chunk is enqueued BEFORE the host waits for this check's
+    // count, so the GPU never idles over the read-back.  If the count turns
+    // out zero, the chunk in flight repeats the fixed point's bytes: the
+    // frame is the same image, reps_done is where the check stood.
+    const int next = std::min(check_every, max_reps - done);
+    if (next > 0) chunk(next);
+    const uint64_t local = finish_residual();
+    st.residual = reduce ? reduce(local) : local;
+    ++st.checks;
+    st.reps_done = done;
+    st.converged = st.residual == 0;
+    if (st.converged || next == 0) break;
+    done += next;
+    check();
+  }
+  synchronize();
+  // the last check's exchange belongs to no later run()
+  sum.exchanges += pre_exchanges_;
+  pre_exchanges_ = 0;
+  sum.wall_ms = (wall_seconds() - w0) * 1e3;
+  sum.loop_ms = sum.wall_ms;  // chunks and checks overlap: the loop is timed as a whole, on the host
+  stats_ = sum;
+  return st;
+}
+
 bool BandEngine::exchange_free(int reps, bool halo_preloaded) const {
   PlanConfig c = engine_plan_config(geom_, band_, filter_, opt_);
   c.halo_preloaded = halo_preloaded;

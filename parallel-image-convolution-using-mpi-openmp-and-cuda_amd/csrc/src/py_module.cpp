@@ -229,6 +229,57 @@ PYBIND11_MODULE(_pconv_native, m) {
       py::arg("filter"), py::arg("channels"), py::arg("row_bytes"), py::arg("rows"), py::arg("halo"), py::arg("src"),
       py::arg("dst"), py::arg("lo"), py::arg("hi"), py::arg("steps"), py::arg("g_row0"), py::arg("height"),
       py::arg("omp") = false, py::arg("border") = "zero");
+  m.def(
+      "cpu_residual",
+      [](py::buffer in, int64_t w, int64_t h, const std::string& ch, py::object filter, bool omp, int threads,
+         const std::string& border) {
+        const ImageGeom g = make_geom(w, h, ch);
+        const Border bd = parse_border(border);
+        const HostView a = host_view(in, false);
+        PCONV_CHECK(a.size == g.bytes(), "buffer size does not match the image geometry");
+        const Filter f = make_filter(filter);
+        py::gil_scoped_release nogil;
+        return cpu_image_residual(f, g, a.ptr, omp ? CpuBackend::OpenMP : CpuBackend::Serial, threads, bd);
+      },
+      py::arg("src"), py::arg("width"), py::arg("height"), py::arg("channels"), py::arg("filter") = "gaussian",
+      py::arg("omp") = false, py::arg("threads") = 0, py::arg("border") = "zero",
+      "bytes of the image that one more repetition would change (0: a fixed point)");
+  m.def(
+      "cpu_frame_residual",
+      [](py::object filter, const std::string& ch, int64_t row_bytes, int64_t rows, int64_t halo, py::buffer src,
+         int64_t r0, int64_t r1, int64_t g_row0, int64_t height, bool omp, const std::string& border) {
+        const Border bd = parse_border(border);
+        const FrameLayout lay = FrameLayout::make(row_bytes, rows, halo);
+        const HostView a = host_view(src, false);
+        PCONV_CHECK(a.size == lay.bytes(), "frame buffer size mismatch");
+        const Filter f = make_filter(filter);
+        py::gil_scoped_release nogil;
+        return cpu_residual(f, parse_channels(ch), lay, a.ptr, r0, r1, omp ? CpuBackend::OpenMP : CpuBackend::Serial, bd,
+                            g_row0, height);
+      },
+      py::arg("filter"), py::arg("channels"), py::arg("row_bytes"), py::arg("rows"), py::arg("halo"), py::arg("src"),
+      py::arg("r0"), py::arg("r1"), py::arg("g_row0"), py::arg("height"), py::arg("omp") = false,
+      py::arg("border") = "zero", "cpu_residual on a band frame (cpu_fused_launch's frame arguments)");
+  m.def(
+      "cpu_convolve_until_stable",
+      [](py::buffer in, py::buffer out, int64_t w, int64_t h, const std::string& ch, int max_reps, int check_every,
+         py::object filter, bool omp, int threads, const std::string& border) {
+        const ImageGeom g = make_geom(w, h, ch);
+        const Border bd = parse_border(border);
+        const HostView a = host_view(in, false), b = host_view(out, true);
+        PCONV_CHECK(a.size == g.bytes() && b.size == g.bytes(), "buffer size does not match the image geometry");
+        const Filter f = make_filter(filter);
+        StableStats st;
+        {
+          py::gil_scoped_release nogil;
+          st = cpu_convolve_until_stable(f, g, a.ptr, b.ptr, max_reps, check_every,
+                                         omp ? CpuBackend::OpenMP : CpuBackend::Serial, threads, bd);
+        }
+        return py::make_tuple(st.reps_done, st.converged, st.residual, st.checks);
+      },
+      py::arg("src"), py::arg("dst"), py::arg("width"), py::arg("height"), py::arg("channels"), py::arg("max_reps"),
+      py::arg("check_every"), py::arg("filter") = "gaussian", py::arg("omp") = false, py::arg("threads") = 0,
+      py::arg("border") = "zero", "(reps_done, converged, residual, checks); dst = the image after reps_done");
   m.def("border_names", []() { return std::vector<std::string>{border_name(Border::Zero), border_name(Border::Replicate)}; },
         "border modes every backend takes (the first is the default and the reference's)");
 
@@ -378,6 +429,40 @@ PYBIND11_MODULE(_pconv_native, m) {
       py::arg("r0"), py::arg("r1"), py::arg("frame_lo"), py::arg("frame_hi"), py::arg("steps") = 1,
       py::arg("g_row0") = 0, py::arg("height") = (int64_t(1) << 40), py::arg("stream") = 0,
       py::arg("variant") = "auto", py::arg("border") = "zero");
+  m.def(
+      "launch_residual",
+      [](py::object filter, const std::string& ch, uintptr_t src, int64_t pitch, int64_t row_bytes, int64_t r0,
+         int64_t r1, int64_t frame_lo, int64_t frame_hi, int64_t g_row0, int64_t height, uintptr_t stream,
+         const std::string& border) {
+        StencilLaunch a;
+        a.border = parse_border(border);
+        a.src = reinterpret_cast<const uint8_t*>(src);
+        a.pitch = pitch;
+        a.row_bytes = row_bytes;
+        a.r0 = r0;
+        a.r1 = r1;
+        a.frame_lo = frame_lo;
+        a.frame_hi = frame_hi;
+        a.g_row0 = g_row0;
+        a.height = height;
+        const Filter f = make_filter(filter);
+        const Channels c = parse_channels(ch);
+        hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+        py::gil_scoped_release nogil;
+        DeviceBuffer counter(16);
+        PCONV_HIP_CHECK(hipMemsetAsync(counter.data(), 0, 16, s));
+        launch_residual(f, c, a, reinterpret_cast<uint64_t*>(counter.data()), s);
+        uint64_t n = 0;
+        PCONV_HIP_CHECK(hipMemcpyAsync(&n, counter.data(), sizeof(n), hipMemcpyDeviceToHost, s));
+        PCONV_HIP_CHECK(hipStreamSynchronize(s));
+        return n;
+      },
+      py::arg("filter"), py::arg("channels"), py::arg("src"), py::arg("pitch"), py::arg("row_bytes"), py::arg("r0"),
+      py::arg("r1"), py::arg("frame_lo"), py::arg("frame_hi"), py::arg("g_row0") = 0,
+      py::arg("height") = (int64_t(1) << 40), py::arg("stream") = 0, py::arg("border") = "zero",
+      "Residual kernel on a frame (launch_stencil's geometry arguments): bytes of rows [r0, r1) that one more "
+      "repetition would change; synchronises the stream.");
+  m.attr("RESIDUAL_BLOCK_ROWS") = kResidualBlockRows;
   m.def("set_swar_shape", &set_swar_shape, py::arg("lw") = 0, py::arg("m") = 0, py::arg("nw") = 0,
         "Force the SWAR temporal tile shape (lw=0: back to the latency model).");
   m.def("swar_shapes", []() {
@@ -551,6 +636,29 @@ PYBIND11_MODULE(_pconv_native, m) {
       .def("signal_stream", [](BandEngine& e, uintptr_t s) { e.signal_stream(reinterpret_cast<hipStream_t>(s)); })
       .def("run", &BandEngine::run, py::arg("reps"), py::call_guard<py::gil_scoped_release>())
       .def("synchronize", &BandEngine::synchronize, py::call_guard<py::gil_scoped_release>())
+      .def("residual", &BandEngine::residual, py::call_guard<py::gil_scoped_release>(),
+           "bytes of this band's owned rows that one more repetition would change (collective over the bands)")
+      .def(
+          "run_until_stable",
+          [](BandEngine& e, int max_reps, int check_every, py::object reduce) {
+            std::function<uint64_t(uint64_t)> red;
+            if (!reduce.is_none())
+              red = [reduce](uint64_t local) {
+                py::gil_scoped_acquire gil;
+                return reduce(local).cast<uint64_t>();
+              };
+            StableStats st;
+            {
+              py::gil_scoped_release nogil;
+              st = e.run_until_stable(max_reps, check_every, red);
+            }
+            return py::make_tuple(st.reps_done, st.converged, st.residual, st.checks);
+          },
+          py::arg("max_reps"), py::arg("check_every"), py::arg("reduce") = py::none(),
+          "(reps_done, converged, residual, checks); reduce(local count) -> sum over the ranks for a band with "
+          "neighbours")
+      .def("time_residual", &BandEngine::time_residual, py::arg("launches"), py::call_guard<py::gil_scoped_release>(),
+           "diagnostics: ms of each of `launches` residual launches on the current frame (stream events)")
       .def("clear", &BandEngine::clear)
       .def_property_readonly("stats", &BandEngine::last_stats)
       .def(

@@ -65,3 +65,11 @@ def numpy_convolve(img: np.ndarray, reps: int = 1, filt="gaussian", border: str 
     for _ in range(int(reps)):
         out = numpy_step(out, filt, border)
     return out
+
+
+def numpy_residual(img: np.ndarray, filt="gaussian", border: str = "zero") -> int:
+    """Bytes of ``img`` that one more repetition would change; 0 means ``img``
+    is a fixed point of the iterated map.  By definition
+    ``count_nonzero(numpy_convolve(img, 1, filt, border) != img)``."""
+    x = np.asarray(img, dtype=np.uint8)
+    return int(np.count_nonzero(numpy_convolve(x, 1, filt, border) != x))

@@ -17,6 +17,7 @@ engine's stream, ordered after/before torch's current stream).
 from __future__ import annotations
 
 from collections import OrderedDict
+from dataclasses import dataclass
 from typing import Optional, Tuple
 
 import numpy as np
@@ -24,7 +25,7 @@ import torch
 
 from .._native import require_native
 from ..models.filters import get_filter
-from .reference import check_border, numpy_convolve
+from .reference import check_border, numpy_convolve, numpy_residual, numpy_step
 
 _CHANNELS = {1: "grey", 3: "rgb", 4: "rgba"}
 
@@ -36,6 +37,30 @@ def image_geometry(shape) -> Tuple[int, int, str]:
     if len(shape) == 3 and int(shape[2]) in _CHANNELS:
         return int(shape[1]), int(shape[0]), _CHANNELS[int(shape[2])]
     raise ValueError(f"unsupported image shape {tuple(shape)}: expected (H, W) or (H, W, 1|3|4)")
+
+
+@dataclass(frozen=True)
+class StableInfo:
+    """Outcome of a run to the fixed point: repetitions actually run, whether
+    the returned image is a fixed point, the last check's count of bytes one
+    more repetition would change (it describes the returned image), and the
+    number of checks made."""
+
+    reps_done: int
+    converged: bool
+    residual: int
+    checks: int
+
+
+# Default check intervals.  CPU backends: a check costs about one repetition,
+# so one per 32 adds ~3 %.  GPU: 16 fused launches per check.  A check is the
+# residual launch (about half a fused launch, as its traffic says) plus ~20 us
+# of read-back and kernel boundaries; at 4 launches per check that measured
+# +28 % on a 1920x2520 RGB loop, at 16 +8.5 % (docs/PERFORMANCE.md 3.2), and
+# the up to 16 x fuse - 1 repetitions run past the fixed point are few against
+# the hundreds to thousands it takes to reach one.
+_CPU_CHECK_EVERY = 32
+_GPU_CHECK_LAUNCHES = 16
 
 
 class Engine:
@@ -99,6 +124,49 @@ class Engine:
         if isinstance(img, torch.Tensor):
             return self.run_tensor(img, reps)
         return self.run_numpy(np.asarray(img), reps)
+
+    # ---- fixed point -------------------------------------------------
+    def _with_frame(self, img, work):
+        """Upload ``img`` (array or tensor), ``work()`` on the resident frame,
+        download the newest frame into the input's container type."""
+        if isinstance(img, torch.Tensor) and img.device.type == "cuda":
+            src = img.contiguous()
+            out = torch.empty_like(src)
+            ts = torch.cuda.current_stream(src.device).cuda_stream
+            self._eng.wait_stream(ts)
+            self._eng.upload_ptr(src.data_ptr(), self.row_bytes, 0, self.height, device=True)
+            res = work()
+            self._eng.download_ptr(out.data_ptr(), self.row_bytes, 0, self.height, device=True)
+            self._eng.signal_stream(ts)
+            src.record_stream(torch.cuda.current_stream(src.device))
+            return out, res
+        is_tensor = isinstance(img, torch.Tensor)
+        src = np.ascontiguousarray(img.numpy() if is_tensor else img, dtype=np.uint8)
+        out = np.empty_like(src)
+        self._eng.upload(src.reshape(-1), 0, self.height)
+        res = work()
+        self._eng.download(out.reshape(-1), 0, self.height)
+        self._eng.synchronize()
+        return (torch.from_numpy(out) if is_tensor else out), res
+
+    def residual(self, img=None) -> int:
+        """Bytes one more repetition would change: of ``img``, or (``None``) of
+        the frame the engine holds after its last run."""
+        if img is None:
+            return int(self._eng.residual())
+        return int(self._with_frame(img, self._eng.residual)[1])
+
+    def run_until_stable(self, img, max_reps: int, check_every: Optional[int] = None):
+        """Repetitions in chunks of ``check_every`` (default 16 x fuse) with a
+        residual check after each, stopping at the first fixed point or at
+        ``max_reps``; returns ``(image, StableInfo)``."""
+        if max_reps < 0:
+            raise ValueError("max_reps must be >= 0")
+        k = _GPU_CHECK_LAUNCHES * self.fuse if check_every is None else int(check_every)
+        if k < 1:
+            raise ValueError("check_every must be >= 1")
+        out, st = self._with_frame(img, lambda: self._eng.run_until_stable(int(max_reps), k))
+        return out, StableInfo(int(st[0]), bool(st[1]), int(st[2]), int(st[3]))
 
 
 _ENGINES: "OrderedDict[tuple, Engine]" = OrderedDict()
@@ -169,6 +237,89 @@ def convolve(image, reps: int = 1, filter="gaussian", backend: str = "auto", dev
         return eng(image, reps)
 
     raise ValueError(f"unknown backend {backend!r} (hip|omp|cpu|numpy|auto)")
+
+
+def _resolve_backend(image, backend: str) -> str:
+    if backend == "auto":
+        is_cuda = isinstance(image, torch.Tensor) and image.is_cuda
+        return "hip" if is_cuda else _default_backend()
+    if backend not in ("hip", "omp", "cpu", "numpy"):
+        raise ValueError(f"unknown backend {backend!r} (hip|omp|cpu|numpy|auto)")
+    return backend
+
+
+def residual(image, filter="gaussian", backend: str = "auto", device: Optional[int] = None, threads: int = 0,
+             border: str = "zero") -> int:
+    """Bytes of ``image`` that one more repetition of ``filter`` would change
+    (0: the image is a fixed point of the iterated map), on any backend."""
+    flt = get_filter(filter)
+    check_border(border)
+    is_tensor = isinstance(image, torch.Tensor)
+    if is_tensor and image.dtype != torch.uint8:
+        raise TypeError("image tensor must be uint8")
+    w, h, ch = image_geometry(tuple(image.shape))
+    backend = _resolve_backend(image, backend)
+    if backend == "hip":
+        if device is None:
+            device = image.device.index if (is_tensor and image.is_cuda) else 0
+        return _cached_engine(w, h, ch, flt, int(device or 0), None, False, "auto", border).residual(image)
+    arr = np.ascontiguousarray(image.cpu().numpy() if is_tensor else image, dtype=np.uint8)
+    if backend == "numpy":
+        return numpy_residual(arr, flt, border)
+    return int(require_native().cpu_residual(arr.reshape(-1), w, h, ch, flt.to_native(), backend == "omp",
+                                             int(threads), border=border))
+
+
+def convolve_until_stable(image, max_reps: int, filter="gaussian", check_every: Optional[int] = None,
+                          backend: str = "auto", device: Optional[int] = None, fuse: Optional[int] = None,
+                          graph: bool = False, variant: str = "auto", threads: int = 0, border: str = "zero"):
+    """``convolve`` that stops at the fixed point of the iterated map.
+
+    Runs chunks of ``check_every`` repetitions (the last one shorter; default
+    16 x the engine's fuse on the GPU, 32 on the CPU backends), counts after
+    each chunk the bytes one more repetition would change, and stops at the
+    first zero or at ``max_reps``.  From a fixed point on every further
+    repetition returns the same bytes, so a converged result equals
+    ``convolve(image, max_reps, ...)``.  Returns ``(out, StableInfo)``.
+    """
+    if max_reps < 0:
+        raise ValueError("max_reps must be >= 0")
+    if check_every is not None and int(check_every) < 1:
+        raise ValueError("check_every must be >= 1")
+    flt = get_filter(filter)
+    check_border(border)
+    is_tensor = isinstance(image, torch.Tensor)
+    if is_tensor and image.dtype != torch.uint8:
+        raise TypeError("image tensor must be uint8")
+    w, h, ch = image_geometry(tuple(image.shape))
+    backend = _resolve_backend(image, backend)
+
+    if backend == "hip":
+        if device is None:
+            device = image.device.index if (is_tensor and image.is_cuda) else 0
+        eng = _cached_engine(w, h, ch, flt, int(device or 0), fuse, graph, variant, border)
+        return eng.run_until_stable(image, int(max_reps), check_every)
+
+    k = _CPU_CHECK_EVERY if check_every is None else int(check_every)
+    arr = np.ascontiguousarray(image.cpu().numpy() if is_tensor else image, dtype=np.uint8)
+    if backend == "numpy":
+        out, done, checks = arr.copy(), 0, 0
+        while True:
+            for _ in range(min(k, int(max_reps) - done)):
+                out = numpy_step(out, flt, border)
+                done += 1
+            res = numpy_residual(out, flt, border)
+            checks += 1
+            if res == 0 or done >= max_reps:
+                break
+        info = StableInfo(done, res == 0, res, checks)
+    else:
+        out = np.empty_like(arr)
+        st = require_native().cpu_convolve_until_stable(arr.reshape(-1), out.reshape(-1), w, h, ch, int(max_reps), k,
+                                                        flt.to_native(), backend == "omp", int(threads),
+                                                        border=border)
+        info = StableInfo(int(st[0]), bool(st[1]), int(st[2]), int(st[3]))
+    return (torch.from_numpy(out).to(image.device) if is_tensor else out), info
 
 
 def convolve_file(path: str, width: int, height: int, reps: int, channels: str = "grey", filter="gaussian",

@@ -99,15 +99,20 @@ def parse(argv: List[str]) -> argparse.Namespace:
     p.add_argument("--checkpoint-every", type=int, default=0, metavar="K",
                    help="every K repetitions write the whole image to <out>.rep<N> (each rank pwrites its band); "
                         "resume = rerun on that file with the remaining repetitions")
+    p.add_argument("--converge-every", type=int, default=0, metavar="K",
+                   help="stop at the fixed point: every K repetitions count the bytes one more repetition would "
+                        "change (summed over the ranks) and end the run at zero; `reps` becomes the maximum")
     p.add_argument("--cpu-bind", action="store_true",
                    help="--backend cpu/omp: bind each rank to its own CPU slice (off by default: unbound teams "
                         "were steadier on a shared host, profiles/r03/hybrid/)")
     p.add_argument("--no-numa-bind", action="store_true",
                    help="--backend hip: leave each rank's CPU affinity alone (default: the GPU's NUMA node)")
     a = p.parse_args(argv)
-    if a.width < 1 or a.height < 1 or a.reps < 0 or a.checkpoint_every < 0:
+    if a.width < 1 or a.height < 1 or a.reps < 0 or a.checkpoint_every < 0 or a.converge_every < 0:
         sys.stderr.write(usage(prog))
         raise SystemExit(1)
+    if a.converge_every > 0 and a.checkpoint_every > 0:
+        p.error("--converge-every cannot be combined with --checkpoint-every")
     return a
 
 
@@ -155,6 +160,13 @@ class _HipBand:
         self.eng.download(out.reshape(-1), 0, self.band.rows)
         self.eng.synchronize()
 
+    def residual(self) -> int:
+        """This band's count (collective: the ghost zone is exchanged first and
+        stays valid for the next run(), whose stats count that exchange)."""
+        return int(self.eng.residual())
+
+    check_exchanges = 0
+
     @property
     def counts(self):
         """(launches, exchanges) of the LAST run() (the caller sums chunks)."""
@@ -194,6 +206,19 @@ class _CpuBand:
 
     def result(self, out: np.ndarray) -> None:
         out.reshape(self.band.rows, -1)[:] = self.r.result()
+
+    def residual(self) -> int:
+        """This band's count (collective): the whole ghost zone is exchanged
+        first, so the next run() starts with it pre-loaded."""
+        r = self.r
+        if self.band.up >= 0 or self.band.down >= 0:
+            r._exchange(r.halo, None)
+            self.check_exchanges += 1
+            self._preloaded = True
+        return int(r.n.cpu_frame_residual(r.filter, r.channels, r.row_bytes, self.band.rows, r.halo, r.frames[r.cur],
+                                          0, self.band.rows, self.band.y0, r.height, r.omp, border=r.border))
+
+    check_exchanges = 0  # exchanges made by residual() (run() counts its own)
 
     @property
     def counts(self):
@@ -256,7 +281,22 @@ def main(argv: Optional[List[str]] = None) -> int:
         t0 = time.perf_counter()
         done = 0
         launches = exchanges = 0  # summed over checkpoint chunks (each run() reports its own)
-        while done < a.reps or (done == 0 and a.reps == 0):
+        cv = a.converge_every
+        res_count = None  # --converge-every: the latest check's count, summed over the ranks
+        while cv > 0:
+            # chunks of K repetitions, a residual check after each (the last
+            # one at `reps` too): every rank sees the same sum and stops alike
+            k = min(cv, a.reps - done)
+            runner.run(k)
+            cl, cx = runner.counts
+            launches += cl
+            exchanges += cx
+            done += k
+            res_count = sum_over_ranks(runner.residual())
+            if res_count == 0 or done >= a.reps:
+                break
+        exchanges += runner.check_exchanges
+        while cv == 0 and (done < a.reps or (done == 0 and a.reps == 0)):
             k = min(ce, a.reps - done) if ce > 0 else a.reps
             runner.run(k)
             cl, cx = runner.counts
@@ -285,7 +325,7 @@ def main(argv: Optional[List[str]] = None) -> int:
                 else:
                     n.read_raw(a.image, src, a.width, a.height, a.channels)
                 ref = np.empty_like(src)
-                n.cpu_convolve(src, ref, a.width, a.height, a.channels, a.reps, get_filter(a.filter).to_native(),
+                n.cpu_convolve(src, ref, a.width, a.height, a.channels, done, get_filter(a.filter).to_native(),
                                True, 0, border=a.border)
                 got = np.empty_like(src)
                 n.read_raw(out_path, got, a.width, a.height, a.channels)
@@ -294,8 +334,13 @@ def main(argv: Optional[List[str]] = None) -> int:
         if rank == 0:
             if not a.quiet:
                 print(f"{t_max:f}", flush=True)  # reference format (mpi_convolution.c:274)
+            if cv > 0 and not a.quiet:
+                print(f"fixed point after {done} repetitions" if res_count == 0 else
+                      f"no fixed point within {done} repetitions ({res_count} bytes still change)",
+                      file=sys.stderr, flush=True)
             if a.json:
-                px = a.width * a.height * a.reps
+                px = a.width * a.height * done
+                stable = {"reps_done": done, "converged": res_count == 0, "residual": res_count} if cv > 0 else {}
                 print(json.dumps({
                     "backend": a.backend, "ranks": world, "width": a.width, "height": a.height,
                     "channels": a.channels, "reps": a.reps, "filter": a.filter, "border": a.border, "loop_s": t_max,
@@ -305,6 +350,7 @@ def main(argv: Optional[List[str]] = None) -> int:
                     "mismatches": mismatches,
                     "rank0_cpus": len(cpus) if cpus is not None else None,
                     "omp_threads": n.cpu_threads() if a.backend == "omp" else None,
+                    **stable,
                 }), flush=True)
         return 0 if not mismatches else 2
     finally:
