@@ -14,6 +14,8 @@
 #pragma once
 
 #include <cstdint>
+#include <functional>
+#include <vector>
 
 #include "pconv/filter.hpp"
 #include "pconv/image.hpp"
@@ -43,6 +45,37 @@ void cpu_step(const Filter& f, Channels ch, const FrameLayout& lay, const uint8_
 void cpu_fused_launch(const Filter& f, Channels ch, const FrameLayout& lay, const uint8_t* src_frame,
                       uint8_t* dst_frame, int64_t lo, int64_t hi, int steps, int64_t g_row0, int64_t height,
                       CpuBackend be, Border border = Border::Zero);
+
+// A whole image on the host: its two zero-padded ping-pong frames
+// (FrameLayout::make(row_bytes, height, 1); the reference's calloc'd buffers,
+// mpi/mpi_convolution.c:104-124) and the loops over them.  Every whole-image
+// CPU path is built on it; the OpenMP team is the caller's.
+class HostFrames {
+ public:
+  HostFrames(const Filter& f, const ImageGeom& geom, CpuBackend be, Border border = Border::Zero);
+  // Allocate both frames zeroed and fill the newest one: from contiguous rows
+  // (pitch == row_bytes), or by fill(row 0 column 0, pitch).
+  void load(const uint8_t* in);
+  void load(const std::function<void(uint8_t* row0, int64_t pitch)>& fill);
+  void release();  // free both frames (load() brings them back)
+  void step();     // one repetition; its result is the newest frame
+  // cpu_residual of the newest frame.
+  uint64_t residual() const;
+  // The newest frame as contiguous rows.
+  void copy_out(uint8_t* out) const;
+  // Chunks of `check_every` repetitions (the last one shorter), residual()
+  // after each, at most max_reps repetitions; the final check is made even at
+  // max_reps (repetitions 0: the input itself is checked).
+  StableStats run_until_stable(int max_reps, int check_every);
+
+ private:
+  Filter f_;
+  ImageGeom geom_;
+  CpuBackend be_;
+  Border border_;
+  FrameLayout lay_;
+  std::vector<uint8_t> cur_, nxt_;
+};
 
 // reps steps on a contiguous image (pitch == row_bytes), zero-padded semantics
 // unless `border` says otherwise.

@@ -267,6 +267,8 @@ class BandEngine {
   // check's count.  One check is outstanding at a time.
   void enqueue_residual();
   uint64_t finish_residual();
+  // launch_residual over the band's owned rows of the current frame.
+  void launch_band_residual();
 
   ImageGeom geom_;
   Band band_;

@@ -8,8 +8,8 @@
 // marches down kRpt rows keeping the three-row window in registers, evaluates
 // step(x) per byte in the project's arithmetic — (sum tap*p) >> shift for
 // int-exact filters, float32 multiply-then-add in row-major tap order
-// otherwise (k_generic9's two forms) — and counts the bytes that differ from
-// x.  No pixel is stored.  Counts are summed in the wave, then across the
+// otherwise (nine_tap.hpp, shared with k_generic9) — and counts the bytes that
+// differ from x.  No pixel is stored.  Counts are summed in the wave, then across the
 // workgroup's four waves through LDS, and one 64-bit atomic add per workgroup
 // (none when its count is zero) lands on the device counter.
 //
@@ -25,34 +25,16 @@
 
 #include "pconv/device.hpp"
 #include "pconv/kernels.hpp"
+#include "nine_tap.hpp"
+#include "tuning.hpp"
 
 namespace pconv {
 namespace {
 
-using u32 = uint32_t;
-
 constexpr int kRpt = kResidualBlockRows / 4;  // rows per lane; 4 waves stacked vertically per workgroup
 
-struct ResTaps {
-  int t[9];
-  float w[9];
-  int shift;
-};
-
-// Row window of one lane: bytes [-4, 20) relative to its first owned byte.
-struct Row24 {
-  u32 w[6];
-};
-
-__device__ __forceinline__ u32 byte_at(const u32 (&w)[6], int b) {  // b in [-4, 20)
-  return (w[(b + 4) >> 2] >> (8 * ((b + 4) & 3))) & 0xffu;
-}
-
-// Mask of the bytes of dword i (positions 4i-4 .. 4i-1) that lie below position n.
-__device__ __forceinline__ u32 below(int i, int n) {
-  const int keep = min(max(n - (4 * i - 4), 0), 4);
-  return keep >= 4 ? 0xffffffffu : ((1u << (8 * keep)) - 1u);
-}
+// Mask of the bytes of window dword i (positions 4i-4 .. 4i-1) that lie below position n.
+__device__ __forceinline__ u32 below(int i, int n) { return low_bytes(n, 4 * i - 4); }
 
 // One frame row with the border rule applied.  `r` is the frame row, [lo, hi)
 // the frame rows inside the global image, x the lane's first byte, valid =
@@ -97,34 +79,12 @@ __device__ __forceinline__ Row24 load_row(const uint8_t* __restrict__ src, int64
 
 // Bytes j < valid of the middle row that one repetition changes.
 template <int CH, bool FLOAT>
-__device__ __forceinline__ u32 changed(const Row24& a, const Row24& b, const Row24& c, const ResTaps& tp, int valid) {
+__device__ __forceinline__ u32 changed(const Row24& a, const Row24& b, const Row24& c, const Taps9& tp, int valid) {
   u32 n = 0;
 #pragma unroll
   for (int j = 0; j < 16; ++j) {
     u32 v;
-    if constexpr (FLOAT) {
-#pragma clang fp contract(off)  // multiply-then-add, one rounding each (reference x86 semantics)
-      float acc = 0.0f;
-#pragma unroll
-      for (int l = 0; l < 3; ++l)
-        acc = __fadd_rn(acc, __fmul_rn(static_cast<float>(byte_at(a.w, j + (l - 1) * CH)), tp.w[l]));
-#pragma unroll
-      for (int l = 0; l < 3; ++l)
-        acc = __fadd_rn(acc, __fmul_rn(static_cast<float>(byte_at(b.w, j + (l - 1) * CH)), tp.w[3 + l]));
-#pragma unroll
-      for (int l = 0; l < 3; ++l)
-        acc = __fadd_rn(acc, __fmul_rn(static_cast<float>(byte_at(c.w, j + (l - 1) * CH)), tp.w[6 + l]));
-      v = acc > 0.0f ? (acc >= 255.0f ? 255u : static_cast<u32>(acc)) : 0u;
-    } else {
-      int acc = 0;
-#pragma unroll
-      for (int l = 0; l < 3; ++l) {
-        acc += tp.t[l] * static_cast<int>(byte_at(a.w, j + (l - 1) * CH));
-        acc += tp.t[3 + l] * static_cast<int>(byte_at(b.w, j + (l - 1) * CH));
-        acc += tp.t[6 + l] * static_cast<int>(byte_at(c.w, j + (l - 1) * CH));
-      }
-      v = static_cast<u32>(min(acc >> tp.shift, 255));
-    }
+    PCONV_NINE_TAP(v, a.w, b.w, c.w, tp, j)
     n += (j < valid && v != byte_at(b.w, j)) ? 1u : 0u;
   }
   return n;
@@ -134,7 +94,7 @@ __device__ __forceinline__ u32 changed(const Row24& a, const Row24& b, const Row
 // flat grid, the row's chunks fastest.
 template <int CH, bool FLOAT, bool REP>
 __global__ __launch_bounds__(256) void k_residual(const uint8_t* __restrict__ src, int64_t pitch, int row_bytes,
-                                                  int r0, int r1, ResTaps tp, int img_lo, int img_hi, int blocks_x,
+                                                  int r0, int r1, Taps9 tp, int img_lo, int img_hi, int blocks_x,
                                                   unsigned long long* __restrict__ counter) {
   __shared__ u32 part[4];
   const int bx = static_cast<int>(blockIdx.x % static_cast<unsigned>(blocks_x));
@@ -166,37 +126,30 @@ __global__ __launch_bounds__(256) void k_residual(const uint8_t* __restrict__ sr
   }
 }
 
+// f(std::bool_constant<b>) for a run-time b.
+template <class F>
+void with_bool(bool b, F&& f) {
+  b ? f(std::true_type{}) : f(std::false_type{});
+}
+
 template <int CH>
 void launch_ch(const Filter& f, const StencilLaunch& a, uint64_t* counter, hipStream_t s) {
   const int64_t rows = a.r1 - a.r0;
-  // frame rows inside the global image (clamped to the frame)
-  const int lo = static_cast<int>(std::max<int64_t>(-a.g_row0, a.frame_lo));
-  const int hi = static_cast<int>(std::min<int64_t>(a.height - a.g_row0, a.frame_hi));
+  const auto [lo, hi] = image_rows_in_frame(a);
   const int64_t bx = ceil_div<int64_t>(ceil_div<int64_t>(a.row_bytes, 16), 64);
   const int64_t by = ceil_div<int64_t>(rows, kResidualBlockRows);
   PCONV_CHECK(bx * by < (int64_t(1) << 31), "launch_residual: too many workgroups for one grid");
-  ResTaps tp;
-  for (int i = 0; i < 9; ++i) {
-    tp.t[i] = f.taps[i];
-    tp.w[i] = f.weights[i];
-  }
-  tp.shift = f.shift;
+  const Taps9 tp = make_taps9(f);
   const dim3 grid(static_cast<unsigned>(bx * by)), block(64, 4);
   auto* ctr = reinterpret_cast<unsigned long long*>(counter);
   const int rb = static_cast<int>(a.row_bytes), r0 = static_cast<int>(a.r0), r1 = static_cast<int>(a.r1);
-  const int nbx = static_cast<int>(bx);
-  // An int-exact filter is bit-identical in either form by definition; the
-  // integer one needs its sums inside 32 bits.
-  const bool fl = !(f.int_exact && f.abs_sum() * 255 < (1 << 30));
-  const bool rep = a.border == Border::Replicate;
-  if (fl && rep)
-    k_residual<CH, true, true><<<grid, block, 0, s>>>(a.src, a.pitch, rb, r0, r1, tp, lo, hi, nbx, ctr);
-  else if (fl)
-    k_residual<CH, true, false><<<grid, block, 0, s>>>(a.src, a.pitch, rb, r0, r1, tp, lo, hi, nbx, ctr);
-  else if (rep)
-    k_residual<CH, false, true><<<grid, block, 0, s>>>(a.src, a.pitch, rb, r0, r1, tp, lo, hi, nbx, ctr);
-  else
-    k_residual<CH, false, false><<<grid, block, 0, s>>>(a.src, a.pitch, rb, r0, r1, tp, lo, hi, nbx, ctr);
+  const int nbx = static_cast<int>(bx), img_lo = lo, img_hi = hi;
+  with_bool(!int_form_allowed(f), [&](auto fl) {
+    with_bool(a.border == Border::Replicate, [&](auto rep) {
+      k_residual<CH, decltype(fl)::value, decltype(rep)::value>
+          <<<grid, block, 0, s>>>(a.src, a.pitch, rb, r0, r1, tp, img_lo, img_hi, nbx, ctr);
+    });
+  });
 }
 
 }  // namespace
@@ -208,23 +161,14 @@ void launch_residual(const Filter& f, Channels ch, const StencilLaunch& a_in, ui
   a.r1 = std::min(a.r1, a.height - a.g_row0);
   if (a.r1 <= a.r0) return;
   // Geometry guards: every access of the launch must stay inside the frame.
-  PCONV_CHECK(a.src && counter, "launch_residual: bad buffers");
   PCONV_CHECK(a.row_bytes >= 1, "launch_residual: empty rows");
-  PCONV_CHECK(a.r0 - 1 >= a.frame_lo && a.r1 + 1 <= a.frame_hi,
-              "launch_residual: rows [" + std::to_string(a.r0) + "," + std::to_string(a.r1) + ") +/- 1 exceed frame [" +
-                  std::to_string(a.frame_lo) + "," + std::to_string(a.frame_hi) + ")");
-  PCONV_CHECK(a.pitch % 16 == 0 && a.pitch >= kPadLeft + round_up<int64_t>(a.row_bytes, 16) + 16,
-              "launch_residual: pitch too small for 16-byte vector access");
+  check_frame_access("launch_residual", a, a.src && counter, 1);
   PCONV_CHECK(reinterpret_cast<uintptr_t>(a.src) % 16 == 0, "launch_residual: frame rows must be 16-byte aligned");
   PCONV_CHECK(a.row_bytes < (int64_t(1) << 31) - 2048 && a.r1 - a.frame_lo < (int64_t(1) << 31) - 64 &&
                   a.r1 < (int64_t(1) << 31) - 64 && a.r0 > -(int64_t(1) << 30),
               "launch_residual: geometry exceeds 32-bit kernel indices");
   PCONV_CHECK(a.row_bytes % channel_count(ch) == 0, "launch_residual: row bytes are no whole pixels");
-  switch (ch) {
-    case Channels::Grey: launch_ch<1>(f, a, counter, stream); break;
-    case Channels::Rgb: launch_ch<3>(f, a, counter, stream); break;
-    case Channels::Rgba: launch_ch<4>(f, a, counter, stream); break;
-  }
+  with_channels(ch, [&](auto chn) { launch_ch<decltype(chn)::value>(f, a, counter, stream); });
   PCONV_HIP_CHECK(hipGetLastError());
 }
 

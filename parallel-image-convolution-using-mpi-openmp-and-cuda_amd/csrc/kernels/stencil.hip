@@ -21,13 +21,12 @@
 
 #include "pconv/kernels.hpp"
 #include "pconv/device.hpp"
+#include "nine_tap.hpp"
 #include "swar.hpp"
 #include "tuning.hpp"
 
 namespace pconv {
 namespace {
-
-using u32 = uint32_t;
 
 __device__ __forceinline__ u32 perm(u32 hi, u32 lo, u32 sel) { return __builtin_amdgcn_perm(hi, lo, sel); }
 
@@ -49,40 +48,36 @@ __device__ __forceinline__ u32 pk_mad2(u32 b, u32 ac) {
   return r;
 }
 
-struct Row16 {
-  u32 L, d0, d1, d2, d3, R;  // bytes [-4,0) , [0,16) , [16,20)
-};
-
 // A row outside the global image reads as zeros whatever the frame holds
 // there (zero-padding semantics, mpi/mpi_convolution.c:111-118): the frame
 // invariant "ghost rows beyond the image edge stay zero" is then not needed
 // for correctness (e.g. a band whose ghost rows a transport filled).
-__device__ __forceinline__ Row16 load_row_in(const uint8_t* __restrict__ p, bool in_image) {
-  Row16 r{0, 0, 0, 0, 0, 0};
+__device__ __forceinline__ Row24 load_row_in(const uint8_t* __restrict__ p, bool in_image) {
+  Row24 r{{0, 0, 0, 0, 0, 0}};
   if (!in_image) return r;
   const uint4 v = *reinterpret_cast<const uint4*>(p);
-  r.L = *reinterpret_cast<const u32*>(p - 4);
-  r.R = *reinterpret_cast<const u32*>(p + 16);
-  r.d0 = v.x;
-  r.d1 = v.y;
-  r.d2 = v.z;
-  r.d3 = v.w;
+  r.w[0] = *reinterpret_cast<const u32*>(p - 4);
+  r.w[5] = *reinterpret_cast<const u32*>(p + 16);
+  r.w[1] = v.x;
+  r.w[2] = v.y;
+  r.w[3] = v.z;
+  r.w[4] = v.w;
   return r;
 }
 
 // Horizontal [1,2,1] pass at tap distance CH over the 16 owned bytes.
 template <int CH>
-__device__ __forceinline__ void horiz(const Row16& b, u32 (&H)[8]) {
+__device__ __forceinline__ void horiz(const Row24& b, u32 (&H)[8]) {
   u32 P[8 + 2 * CH];
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    P[CH + k] = perm(b.d2, b.d0, pair_sel(k));
-    P[CH + 4 + k] = perm(b.d3, b.d1, pair_sel(k));
+    P[CH + k] = perm(b.w[3], b.w[1], pair_sel(k));
+    P[CH + 4 + k] = perm(b.w[4], b.w[2], pair_sel(k));
   }
 #pragma unroll
-  for (int j = 1; j <= CH; ++j) P[CH - j] = perm(b.d1, b.L, pair_sel(4 - j));  // (b_{-j}, b_{8-j})
+  for (int j = 1; j <= CH; ++j) P[CH - j] = perm(b.w[2], b.w[0], pair_sel(4 - j));  // (b_{-j}, b_{8-j})
 #pragma unroll
-  for (int j = 0; j < CH; ++j) P[CH + 8 + j] = perm(b.R, b.d2, pair_sel(j));   // (b_{8+j}, b_{16+j})
+  for (int j = 0; j < CH; ++j) P[CH + 8 + j] = perm(b.w[5], b.w[3], pair_sel(j));   // (b_{8+j}, b_{16+j})
 #pragma unroll
   for (int k = 0; k < 8; ++k) H[k] = pk_mad2(P[CH + k], pk_add(P[k], P[2 * CH + k]));
 }
@@ -108,11 +103,7 @@ __device__ __forceinline__ uint4 pack16(const u32 (&V)[8]) {
 __device__ __forceinline__ uint4 mask_tail(uint4 o, int valid) {
   u32 w[4] = {o.x, o.y, o.z, o.w};
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int keep = min(max(valid - 4 * i, 0), 4);
-    const u32 m = keep >= 4 ? 0xffffffffu : ((1u << (8 * keep)) - 1u);
-    w[i] &= m;
-  }
+  for (int i = 0; i < 4; ++i) w[i] &= low_bytes(valid, 4 * i);
   return make_uint4(w[0], w[1], w[2], w[3]);
 }
 
@@ -161,16 +152,6 @@ __global__ __launch_bounds__(256) void k_binomial(const uint8_t* __restrict__ sr
 // ---------------------------------------------------------------------------
 // Generic 9-tap (integer-exact or float32) — one row x 16 bytes per lane.
 // ---------------------------------------------------------------------------
-struct Taps9 {
-  int t[9];
-  float w[9];
-  int shift;
-};
-
-__device__ __forceinline__ u32 byte_at(const u32 (&w)[6], int b) {  // b in [-4, 20)
-  return (w[(b + 4) >> 2] >> (8 * ((b + 4) & 3))) & 0xffu;
-}
-
 template <int CH, bool FLOAT>
 __global__ __launch_bounds__(256) void k_generic9(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
                                                   int64_t pitch, int row_bytes, int r0, int r1, Taps9 tp,
@@ -178,41 +159,17 @@ __global__ __launch_bounds__(256) void k_generic9(const uint8_t* __restrict__ sr
   const int x = (blockIdx.x * 64 + threadIdx.x) * 16;
   const int r = r0 + blockIdx.y * 4 + threadIdx.y;
   if (x >= row_bytes || r >= r1) return;
-  u32 rows[3][6];
+  Row24 rows[3];
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     const int rr = r - 1 + k;
-    const Row16 b = load_row_in(src + static_cast<int64_t>(rr) * pitch + x, rr >= img_lo && rr < img_hi);
-    rows[k][0] = b.L;
-    rows[k][1] = b.d0;
-    rows[k][2] = b.d1;
-    rows[k][3] = b.d2;
-    rows[k][4] = b.d3;
-    rows[k][5] = b.R;
+    rows[k] = load_row_in(src + static_cast<int64_t>(rr) * pitch + x, rr >= img_lo && rr < img_hi);
   }
   u32 out[4] = {0, 0, 0, 0};
 #pragma unroll
   for (int j = 0; j < 16; ++j) {
     u32 v;
-    if constexpr (FLOAT) {
-#pragma clang fp contract(off)  // multiply-then-add, one rounding each (reference x86 semantics)
-      float acc = 0.0f;
-#pragma unroll
-      for (int k = 0; k < 3; ++k)
-#pragma unroll
-        for (int l = 0; l < 3; ++l) {
-          const float pv = static_cast<float>(byte_at(rows[k], j + (l - 1) * CH));
-          acc = __fadd_rn(acc, __fmul_rn(pv, tp.w[k * 3 + l]));  // reference order, no FMA
-        }
-      v = acc > 0.0f ? (acc >= 255.0f ? 255u : static_cast<u32>(acc)) : 0u;
-    } else {
-      int acc = 0;
-#pragma unroll
-      for (int k = 0; k < 3; ++k)
-#pragma unroll
-        for (int l = 0; l < 3; ++l) acc += tp.t[k * 3 + l] * static_cast<int>(byte_at(rows[k], j + (l - 1) * CH));
-      v = static_cast<u32>(min(acc >> tp.shift, 255));
-    }
+    PCONV_NINE_TAP(v, rows[0].w, rows[1].w, rows[2].w, tp, j)
     out[j >> 2] |= v << (8 * (j & 3));
   }
   uint4 o = make_uint4(out[0], out[1], out[2], out[3]);
@@ -226,9 +183,7 @@ constexpr int kRowsPerLane = 4;
 template <int CH>
 void launch_ch(const Filter& f, const StencilLaunch& a, hipStream_t s, KernelVariant v) {
   const int rows = static_cast<int>(a.r1 - a.r0);
-  // frame rows inside the global image (clamped to the frame; 32-bit indices checked by the caller)
-  const int lo = static_cast<int>(std::max<int64_t>(-a.g_row0, a.frame_lo));
-  const int hi = static_cast<int>(std::min<int64_t>(a.height - a.g_row0, a.frame_hi));
+  const auto [lo, hi] = image_rows_in_frame(a);
   const int chunks = static_cast<int>(ceil_div<int64_t>(a.row_bytes, 16));
   const dim3 block(64, 4);
   if (v == KernelVariant::Binomial) {
@@ -236,12 +191,7 @@ void launch_ch(const Filter& f, const StencilLaunch& a, hipStream_t s, KernelVar
     k_binomial<CH, kRowsPerLane><<<grid, block, 0, s>>>(a.src, a.dst, a.pitch, static_cast<int>(a.row_bytes),
                                                          static_cast<int>(a.r0), static_cast<int>(a.r1), lo, hi);
   } else {
-    Taps9 tp;
-    for (int i = 0; i < 9; ++i) {
-      tp.t[i] = f.taps[i];
-      tp.w[i] = f.weights[i];
-    }
-    tp.shift = f.shift;
+    const Taps9 tp = make_taps9(f);
     const dim3 grid(ceil_div(chunks, 64), ceil_div(rows, 4));
     if (v == KernelVariant::Float9)
       k_generic9<CH, true><<<grid, block, 0, s>>>(a.src, a.dst, a.pitch, static_cast<int>(a.row_bytes),
@@ -322,14 +272,8 @@ void launch_stencil(const Filter& f, Channels ch, const StencilLaunch& a_in, hip
   StencilLaunch a = a_in;
   if (!resolve_launch(f, a, v)) return;
   // Geometry guards: every access of the launch must stay inside the frame.
-  PCONV_CHECK(a.src && a.dst && a.src != a.dst, "launch_stencil: bad buffers");
   PCONV_CHECK(a.steps >= 1, "launch_stencil: steps must be >= 1");
-  PCONV_CHECK(a.r0 - a.steps >= a.frame_lo && a.r1 + a.steps <= a.frame_hi,
-              "launch_stencil: rows [" + std::to_string(a.r0) + "," + std::to_string(a.r1) + ") +/- " +
-                  std::to_string(a.steps) + " exceed frame [" + std::to_string(a.frame_lo) + "," +
-                  std::to_string(a.frame_hi) + ")");
-  PCONV_CHECK(a.pitch % 16 == 0 && a.pitch >= kPadLeft + round_up<int64_t>(a.row_bytes, 16) + 16,
-              "launch_stencil: pitch too small for 16-byte vector access");
+  check_frame_access("launch_stencil", a, a.src && a.dst && a.src != a.dst, a.steps);
   PCONV_CHECK(a.row_bytes < (int64_t(1) << 31) && a.r1 - a.frame_lo < (int64_t(1) << 31),
               "launch_stencil: geometry exceeds 32-bit kernel indices");
   PCONV_CHECK(a.border == Border::Zero || v == KernelVariant::Temporal || v == KernelVariant::FloatTemporal,
@@ -353,7 +297,7 @@ void launch_stencil(const Filter& f, Channels ch, const StencilLaunch& a_in, hip
   if (v == KernelVariant::Binomial)
     PCONV_CHECK(f.binomial121, "binomial kernel requires the gaussian filter");
   if (v == KernelVariant::Int9)
-    PCONV_CHECK(f.int_exact && f.abs_sum() * 255 < (1 << 30), "int9 kernel requires an int-exact filter");
+    PCONV_CHECK(int_form_allowed(f), "int9 kernel requires an int-exact filter");
   with_channels(ch, [&](auto chn) { launch_ch<decltype(chn)::value>(f, a, stream, v); });
   PCONV_HIP_CHECK(hipGetLastError());
 }

@@ -15,6 +15,7 @@
 #include <cinttypes>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <sstream>
 #include <thread>
 
@@ -101,13 +102,11 @@ AppReport run_cpu(const CliConfig& c) {
   const CpuBackend be = c.backend == Backend::Omp ? CpuBackend::OpenMP : CpuBackend::Serial;
   AppReport r;
   r.kernel = be == CpuBackend::OpenMP ? "cpu-omp" : "cpu-serial";
-  // Zero-padded ping-pong frames (the reference's calloc'd buffers,
-  // mpi/mpi_convolution.c:104-124) set up outside the timed loop, like its
-  // MPI_Wtime bracket (:151-154,242); the OpenMP team is started first.
-  const int64_t rb = g.row_bytes();
-  const FrameLayout lay = FrameLayout::make(rb, g.height, 1);
-  std::vector<uint8_t> fa(static_cast<size_t>(lay.bytes()), 0), fb(static_cast<size_t>(lay.bytes()), 0);
-  for (int64_t y = 0; y < g.height; ++y) std::memcpy(fa.data() + lay.offset(y), img.data() + y * rb, rb);
+  // The ping-pong frames are set up outside the timed loop, like the
+  // reference's MPI_Wtime bracket (mpi/mpi_convolution.c:151-154,242); the
+  // OpenMP team is started first.
+  HostFrames fr(f, g, be, c.border);
+  fr.load(img.data());
   if (be == CpuBackend::OpenMP) {
     if (c.threads > 0)
       omp_set_num_threads(c.threads);
@@ -116,35 +115,25 @@ AppReport run_cpu(const CliConfig& c) {
 #pragma omp parallel
     { (void)omp_get_thread_num(); }
   }
-  uint8_t* src = fa.data();
-  uint8_t* dst = fb.data();
-  auto copy_out = [&] {
-    for (int64_t y = 0; y < g.height; ++y) std::memcpy(img.data() + y * rb, src + lay.offset(y), rb);
-  };
   const double l0 = wall_seconds();
-  for (int done = 0; done < c.reps;) {
-    cpu_step(f, g.channels, lay, src, dst, 0, g.height, be, c.border, 0, g.height);
-    std::swap(src, dst);  // newest result is always `src`
-    ++done;
-    if (c.checkpoint_every > 0 && done % c.checkpoint_every == 0 && done < c.reps) {
-      copy_out();
-      write_image(out_path(c) + ".rep" + std::to_string(done), g, img.data());
-    }
+  if (c.converge_every > 0) {
     // --converge-every K: the residual of the newest frame every K
     // repetitions and after the last one; the loop ends at the first zero.
-    if (c.converge_every > 0 && (done % c.converge_every == 0 || done == c.reps)) {
-      r.residual = cpu_residual(f, g.channels, lay, src, 0, g.height, be, c.border, 0, g.height);
-      r.reps_done = done;
-      if (r.residual == 0) break;
+    const StableStats st = fr.run_until_stable(c.reps, c.converge_every);
+    r.reps_done = st.reps_done;
+    r.residual = st.residual;
+    r.converged = st.converged;
+  } else {
+    for (int done = 1; done <= c.reps; ++done) {
+      fr.step();
+      if (c.checkpoint_every > 0 && done % c.checkpoint_every == 0 && done < c.reps) {
+        fr.copy_out(img.data());
+        write_image(out_path(c) + ".rep" + std::to_string(done), g, img.data());
+      }
     }
   }
-  if (c.converge_every > 0 && r.reps_done < 0) {  // (repetitions 0: the input itself is checked)
-    r.residual = cpu_residual(f, g.channels, lay, src, 0, g.height, be, c.border, 0, g.height);
-    r.reps_done = 0;
-  }
-  r.converged = c.converge_every > 0 && r.residual == 0;
   r.loop_s = wall_seconds() - l0;
-  copy_out();
+  fr.copy_out(img.data());
   r.output = out_path(c);
   write_image(r.output, g, img.data());
   if (c.check) r.mismatches = compare_with_oracle(c, g, img.data(), r.reps_done);
@@ -233,6 +222,49 @@ JobCache* new_job_cache(int device, int max_engines) {
 void delete_job_cache(JobCache* c) { delete c; }
 
 namespace {
+
+// An engine's repetitions in chunks, for the one-GPU path and for a rank of
+// the N-GPU one; the hooks are what differs between them.
+struct ChunkHooks {
+  std::function<void()> poll;                // a chunk is enqueued, the host has not waited yet (RCCL errors)
+  std::function<void()> check;               // the host has waited (the IPC transport's check())
+  std::function<uint64_t(uint64_t)> reduce;  // --converge-every: the sum of the ranks' counts (none: one band)
+  std::function<void(int)> after_chunk;      // `done` repetitions made, more to come: the checkpoint
+  bool run_when_empty = false;               // repetitions 0 still enqueue one (empty) run
+};
+struct ChunkedRun {
+  int launches = 0, exchanges = 0;
+  StableStats stable;  // --converge-every only
+};
+
+// --converge-every K: chunks of K repetitions with a residual launch between
+// them (BandEngine::run_until_stable).  Otherwise chunks of
+// --checkpoint-every repetitions, or all of them at once.
+ChunkedRun run_chunks(const CliConfig& c, BandEngine& eng, const ChunkHooks& h) {
+  ChunkedRun out;
+  if (c.converge_every > 0) {
+    out.stable = eng.run_until_stable(c.reps, c.converge_every, h.reduce, h.poll);
+    if (h.check) h.check();
+    out.launches = eng.last_stats().launches;
+    out.exchanges = eng.last_stats().exchanges;
+    return out;
+  }
+  if (c.reps <= 0 && !h.run_when_empty) return out;
+  const int chunk = c.checkpoint_every > 0 ? c.checkpoint_every : std::max(1, c.reps);
+  int done = 0;
+  do {
+    const int k = std::min(chunk, c.reps - done);
+    eng.run(k);
+    if (h.poll) h.poll();
+    eng.synchronize();
+    if (h.check) h.check();
+    out.launches += eng.last_stats().launches;
+    out.exchanges += eng.last_stats().exchanges;
+    done += k;
+    if (c.checkpoint_every > 0 && done < c.reps) h.after_chunk(done);
+  } while (done < c.reps);
+  return out;
+}
 
 // Ring staging of large one-shot images (run_gpu1): kRingSlots pinned
 // chunks of CliConfig::ring_chunk_bytes (--ring-chunk-bytes; 0 = one pinned
@@ -353,28 +385,18 @@ AppReport run_gpu1(const CliConfig& c, JobCache* cache) {
   pc.mark(ring ? "read_and_h2d" : "h2d");
   r.output = out_path(c);
   const double l0 = wall_seconds();
-  int done = 0;
-  const int chunk = c.checkpoint_every > 0 ? c.checkpoint_every : std::max(1, c.reps);
-  if (c.converge_every > 0) {
-    // chunks of K repetitions as above, a residual launch between them
-    const StableStats st = eng.run_until_stable(c.reps, c.converge_every);
-    r.launches = eng.last_stats().launches;
-    r.reps_done = st.reps_done;
-    r.converged = st.converged;
-    r.residual = st.residual;
-    done = c.reps;
-  }
-  while (done < c.reps) {
-    const int k = std::min(chunk, c.reps - done);
-    eng.run(k);
+  ChunkHooks hooks;
+  hooks.after_chunk = [&](int done) {
+    eng.download_rows(host, g.row_bytes(), 0, g.height);
     eng.synchronize();
-    r.launches += eng.last_stats().launches;
-    done += k;
-    if (c.checkpoint_every > 0 && done < c.reps) {
-      eng.download_rows(host, g.row_bytes(), 0, g.height);
-      eng.synchronize();
-      write_image(r.output + ".rep" + std::to_string(done), g, host);
-    }
+    write_image(r.output + ".rep" + std::to_string(done), g, host);
+  };
+  const ChunkedRun cr = run_chunks(c, eng, hooks);
+  r.launches = cr.launches;
+  if (c.converge_every > 0) {
+    r.reps_done = cr.stable.reps_done;
+    r.converged = cr.stable.converged;
+    r.residual = cr.stable.residual;
   }
   r.loop_s = wall_seconds() - l0;
   pc.mark("loop");
@@ -439,7 +461,6 @@ AppReport run_auto(const CliConfig& c) {
   if (!c.synthetic) validate_input_file(c.image, g);
   const Filter f = Filter::by_name(c.filter);
   const int64_t rb = g.row_bytes();
-  const FrameLayout lay = FrameLayout::make(rb, g.height, 1);
   if (c.threads > 0)
     omp_set_num_threads(c.threads);
   else
@@ -504,15 +525,13 @@ AppReport run_auto(const CliConfig& c) {
 
   // Stage 2: the whole image on the host; the first repetition is timed on
   // the full frame and re-prices the job.
-  std::vector<uint8_t> fa(static_cast<size_t>(lay.bytes()), 0), fb(static_cast<size_t>(lay.bytes()), 0);
-  load_rows(c, g, 0, g.height, fa.data() + lay.offset(0), lay.pitch);
+  HostFrames fr(f, g, CpuBackend::OpenMP, c.border);
+  auto fill = [&](uint8_t* row0, int64_t pitch) { load_rows(c, g, 0, g.height, row0, pitch); };
+  fr.load(fill);
   pc.mark(c.synthetic ? "synthesize" : "read");
-  uint8_t* src = fa.data();
-  uint8_t* dst = fb.data();
   int done = 0;
   auto cpu_rep = [&] {
-    cpu_step(f, g.channels, lay, src, dst, 0, g.height, CpuBackend::OpenMP, c.border, 0, g.height);
-    std::swap(src, dst);  // newest result is always `src`
+    fr.step();
     ++done;
   };
   double l0 = wall_seconds();
@@ -528,15 +547,10 @@ AppReport run_auto(const CliConfig& c) {
       std::snprintf(est, sizeof(est), "cpu estimate %.4f s from the first full repetition", cpu_s);
     }
     if (first * (c.reps - 1) >= thr) {
-      std::vector<uint8_t>().swap(fa);  // the GPU path stages the image itself
-      std::vector<uint8_t>().swap(fb);
+      fr.release();  // the GPU path stages the image itself
       if (gpu_alone()) return gr;
       gpu_failed = true;
-      fa.assign(static_cast<size_t>(lay.bytes()), 0);  // back to the CPU: the frames again
-      fb.assign(static_cast<size_t>(lay.bytes()), 0);
-      load_rows(c, g, 0, g.height, fa.data() + lay.offset(0), lay.pitch);
-      src = fa.data();
-      dst = fb.data();
+      fr.load(fill);  // back to the CPU: the frames again
       done = 0;
       l0 = wall_seconds();
       cpu_rep();
@@ -549,7 +563,7 @@ AppReport run_auto(const CliConfig& c) {
   r.loop_s = wall_seconds() - l0;
   pc.mark("cpu_loop");
   std::vector<uint8_t> img(static_cast<size_t>(g.bytes()));
-  for (int64_t y = 0; y < g.height; ++y) std::memcpy(img.data() + y * rb, src + lay.offset(y), static_cast<size_t>(rb));
+  fr.copy_out(img.data());
   write_image(r.output, g, img.data());
   pc.mark("write");
   r.e2e_s = wall_seconds() - t0;
@@ -717,58 +731,42 @@ void run_rank(const CliConfig& c, SharedState* sh, uint8_t* halo_slots, int64_t 
   // chunk but the last every rank pwrites its band into <out>.rep<done>
   // (pre-sized by the launcher).  A later chunk exchanges its ghost rows
   // (run() invalidates the pre-loaded ones).
-  const int chunk = c.checkpoint_every > 0 ? c.checkpoint_every : std::max(1, c.reps);
-  int done = 0, launches = 0, exchanges = 0;
-  if (c.converge_every > 0) {
-    // Chunks of K repetitions with a residual check after each: every rank
-    // publishes its count, all meet, every rank sums the counts and so takes
-    // the same decision (the reference family's MPI_Allreduce); the second
-    // barrier keeps the next check's counts apart.
-    auto reduce = [&](uint64_t local) {
-      sh->residual[rank] = local;
-      shm_barrier(sh, world, c.timeout_s);
-      uint64_t sum = 0;
-      for (int i = 0; i < world; ++i) sum += sh->residual[i];
-      shm_barrier(sh, world, c.timeout_s);
-      return sum;
-    };
-    auto poll = [&] {
-      if (comm) {
-        comm->wait(eng.compute_stream(), c.timeout_s);
-        comm->wait(eng.comm_stream(), c.timeout_s);
-      }
-    };
-    const StableStats st = eng.run_until_stable(c.reps, c.converge_every, reduce, poll);
-    if (ipct) ipct->check();
-    launches = eng.last_stats().launches;
-    exchanges = eng.last_stats().exchanges;
-    if (rank == 0) {
-      sh->reps_done = st.reps_done;
-      sh->converged = st.converged ? 1 : 0;
-      sh->residual_sum = st.residual;
-    }
-    done = c.reps;
-  } else do {
-    const int k = std::min(chunk, c.reps - done);
-    eng.run(k);
+  ChunkHooks hooks;
+  hooks.run_when_empty = true;  // every rank runs the same phases
+  hooks.poll = [&] {
     if (comm) {
       comm->wait(eng.compute_stream(), c.timeout_s);
       comm->wait(eng.comm_stream(), c.timeout_s);
     }
-    eng.synchronize();
+  };
+  hooks.check = [&] {
     if (ipct) ipct->check();
-    launches += eng.last_stats().launches;
-    exchanges += eng.last_stats().exchanges;
-    done += k;
-    if (c.checkpoint_every > 0 && done < c.reps) {
-      eng.download_rows(host.data(), rb, 0, b.rows);
-      eng.synchronize();
-      write_rows(out_path(c) + ".rep" + std::to_string(done), g, b.y0, b.rows, host.data(), rb);
-    }
-  } while (done < c.reps);
+  };
+  // A residual check: every rank publishes its count, all meet, every rank
+  // sums the counts and so takes the same decision (the reference family's
+  // MPI_Allreduce); the second barrier keeps the next check's counts apart.
+  hooks.reduce = [&](uint64_t local) {
+    sh->residual[rank] = local;
+    shm_barrier(sh, world, c.timeout_s);
+    uint64_t sum = 0;
+    for (int i = 0; i < world; ++i) sum += sh->residual[i];
+    shm_barrier(sh, world, c.timeout_s);
+    return sum;
+  };
+  hooks.after_chunk = [&](int done) {
+    eng.download_rows(host.data(), rb, 0, b.rows);
+    eng.synchronize();
+    write_rows(out_path(c) + ".rep" + std::to_string(done), g, b.y0, b.rows, host.data(), rb);
+  };
+  const ChunkedRun cr = run_chunks(c, eng, hooks);
+  if (c.converge_every > 0 && rank == 0) {
+    sh->reps_done = cr.stable.reps_done;
+    sh->converged = cr.stable.converged ? 1 : 0;
+    sh->residual_sum = cr.stable.residual;
+  }
   sh->loop_s[rank] = wall_seconds() - l0;
-  sh->launches[rank] = launches;
-  sh->exchanges[rank] = exchanges;
+  sh->launches[rank] = cr.launches;
+  sh->exchanges[rank] = cr.exchanges;
   eng.download_rows(host.data(), rb, 0, b.rows);
   eng.synchronize();
   {

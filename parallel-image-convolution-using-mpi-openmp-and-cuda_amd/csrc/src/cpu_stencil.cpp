@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 namespace pconv {
@@ -177,68 +178,83 @@ void replicate_rows(const FrameLayout& lay, const uint8_t* src, int64_t r, int64
   b = edge_padded<CH>(pb, n, rows3.data() + w);
 }
 
+// The three input rows of frame row r (columns -CH .. n + CH readable).
+// Replicate: replicate_rows.  Zero: the frame's rows as they are (its ghost
+// rows and pad columns are the border), unless zero_outside: then a row
+// outside the global image is a row of zeros, whatever the frame holds there.
 template <int CH>
-void step_rows(const Filter& f, const FrameLayout& lay, const uint8_t* src, uint8_t* dst, int64_t r0, int64_t r1,
-               CpuBackend be, Border border, int64_t g_row0, int64_t height) {
-  const int64_t n = lay.row_bytes;
-  auto body = [&](int64_t r) {
-    const uint8_t* a = src + lay.offset(r - 1);
-    const uint8_t* b = src + lay.offset(r);
-    const uint8_t* c = src + lay.offset(r + 1);
-    uint8_t* o = dst + lay.offset(r);
-    if (border == Border::Replicate) replicate_rows<CH>(lay, src, r, g_row0, height, a, b, c);
-    eval_row<CH>(f, a, b, c, o, n);
-  };
-  if (be == CpuBackend::OpenMP) {
-    // Below ~32 KiB of output a step is a few microseconds on one core: the
-    // team's fork/join costs as much, and on a loaded host a preempted team
-    // member stalls the barrier for a whole scheduler slice.
-    const bool team = (r1 - r0) * n >= (int64_t{32} << 10);
-#pragma omp parallel for schedule(static) if (team)
-    for (int64_t r = r0; r < r1; ++r) body(r);
-  } else {
-    for (int64_t r = r0; r < r1; ++r) body(r);
+void input_rows(const FrameLayout& lay, const uint8_t* src, int64_t r, Border border, int64_t g_row0, int64_t height,
+                bool zero_outside, const uint8_t*& a, const uint8_t*& b, const uint8_t*& c) {
+  a = src + lay.offset(r - 1);
+  b = src + lay.offset(r);
+  c = src + lay.offset(r + 1);
+  if (border == Border::Replicate) {
+    replicate_rows<CH>(lay, src, r, g_row0, height, a, b, c);
+  } else if (zero_outside) {
+    const int64_t g = g_row0 + r;
+    if (g - 1 < 0 || g + 1 >= height) {
+      thread_local std::vector<uint8_t> zeros;
+      const size_t w = static_cast<size_t>(lay.row_bytes + 2 * CH);
+      if (zeros.size() < w) zeros.assign(w, 0);
+      if (g - 1 < 0) a = zeros.data() + CH;
+      if (g + 1 >= height) c = zeros.data() + CH;
+    }
   }
 }
 
-// step_rows' evaluation into a scratch row, compared with the source row and
-// counted.  Zero border: a row outside the global image is a row of zeros,
-// whatever the frame holds there.
-template <int CH>
-uint64_t residual_rows(const Filter& f, const FrameLayout& lay, const uint8_t* src, int64_t r0, int64_t r1,
-                       CpuBackend be, Border border, int64_t g_row0, int64_t height) {
-  const int64_t n = lay.row_bytes;
-  auto body = [&](int64_t r) -> uint64_t {
-    thread_local std::vector<uint8_t> scratch, zeros;
-    if (scratch.size() < static_cast<size_t>(n)) scratch.resize(static_cast<size_t>(n));
-    const uint8_t* a = src + lay.offset(r - 1);
-    const uint8_t* b = src + lay.offset(r);
-    const uint8_t* c = src + lay.offset(r + 1);
-    if (border == Border::Replicate) {
-      replicate_rows<CH>(lay, src, r, g_row0, height, a, b, c);
-    } else {
-      const int64_t g = g_row0 + r;
-      if (g - 1 < 0 || g + 1 >= height) {
-        if (zeros.size() < static_cast<size_t>(n + 2 * CH)) zeros.assign(static_cast<size_t>(n + 2 * CH), 0);
-        if (g - 1 < 0) a = zeros.data() + CH;
-        if (g + 1 >= height) c = zeros.data() + CH;
-      }
-    }
-    uint8_t* o = scratch.data();
-    eval_row<CH>(f, a, b, c, o, n);
-    uint64_t cnt = 0;
-    for (int64_t x = 0; x < n; ++x) cnt += o[x] != b[x];
-    return cnt;
-  };
+// Sum of body(r) over rows [r0, r1) of n bytes each: serial, or an OpenMP
+// team.  Below ~32 KiB a pass over the rows is a few microseconds on one
+// core: the team's fork/join costs as much, and on a loaded host a preempted
+// team member stalls the barrier for a whole scheduler slice.
+template <class Body>
+uint64_t sum_rows(int64_t r0, int64_t r1, int64_t n, CpuBackend be, Body&& body) {
   uint64_t total = 0;
   if (be == CpuBackend::OpenMP) {
-    const bool team = (r1 - r0) * n >= (int64_t{32} << 10);  // as in step_rows
+    const bool team = (r1 - r0) * n >= (int64_t{32} << 10);
 #pragma omp parallel for schedule(static) reduction(+ : total) if (team)
     for (int64_t r = r0; r < r1; ++r) total += body(r);
   } else {
     for (int64_t r = r0; r < r1; ++r) total += body(r);
   }
   return total;
+}
+
+template <int CH>
+void step_rows(const Filter& f, const FrameLayout& lay, const uint8_t* src, uint8_t* dst, int64_t r0, int64_t r1,
+               CpuBackend be, Border border, int64_t g_row0, int64_t height) {
+  (void)sum_rows(r0, r1, lay.row_bytes, be, [&](int64_t r) -> uint64_t {
+    const uint8_t *a, *b, *c;
+    input_rows<CH>(lay, src, r, border, g_row0, height, false, a, b, c);
+    eval_row<CH>(f, a, b, c, dst + lay.offset(r), lay.row_bytes);
+    return 0;
+  });
+}
+
+// step_rows' evaluation into a scratch row, compared with the source row and
+// counted.
+template <int CH>
+uint64_t residual_rows(const Filter& f, const FrameLayout& lay, const uint8_t* src, int64_t r0, int64_t r1,
+                       CpuBackend be, Border border, int64_t g_row0, int64_t height) {
+  const int64_t n = lay.row_bytes;
+  return sum_rows(r0, r1, n, be, [&](int64_t r) -> uint64_t {
+    thread_local std::vector<uint8_t> scratch;
+    if (scratch.size() < static_cast<size_t>(n)) scratch.resize(static_cast<size_t>(n));
+    const uint8_t *a, *b, *c;
+    input_rows<CH>(lay, src, r, border, g_row0, height, true, a, b, c);
+    uint8_t* o = scratch.data();
+    eval_row<CH>(f, a, b, c, o, n);
+    uint64_t cnt = 0;
+    for (int64_t x = 0; x < n; ++x) cnt += o[x] != b[x];
+    return cnt;
+  });
+}
+
+// fn(std::integral_constant<int, bytes per pixel>) for the channel layout.
+template <class F>
+auto with_channels(Channels ch, F&& fn) {
+  using std::integral_constant;
+  return ch == Channels::Grey ? fn(integral_constant<int, 1>{})
+                              : ch == Channels::Rgb ? fn(integral_constant<int, 3>{}) : fn(integral_constant<int, 4>{});
 }
 
 }  // namespace
@@ -250,12 +266,9 @@ uint64_t cpu_residual(const Filter& f, Channels ch, const FrameLayout& lay, cons
   r1 = std::min(r1, height - g_row0);
   if (r1 <= r0) return 0;
   PCONV_CHECK(r0 >= -lay.halo + 1 && r1 <= lay.rows + lay.halo - 1, "cpu_residual: rows out of frame");
-  switch (ch) {
-    case Channels::Grey: return residual_rows<1>(f, lay, src_frame, r0, r1, be, border, g_row0, height);
-    case Channels::Rgb: return residual_rows<3>(f, lay, src_frame, r0, r1, be, border, g_row0, height);
-    case Channels::Rgba: return residual_rows<4>(f, lay, src_frame, r0, r1, be, border, g_row0, height);
-  }
-  return 0;
+  return with_channels(ch, [&](auto chn) {
+    return residual_rows<decltype(chn)::value>(f, lay, src_frame, r0, r1, be, border, g_row0, height);
+  });
 }
 
 void cpu_step(const Filter& f, Channels ch, const FrameLayout& lay, const uint8_t* src_frame, uint8_t* dst_frame,
@@ -265,11 +278,9 @@ void cpu_step(const Filter& f, Channels ch, const FrameLayout& lay, const uint8_
   if (border != Border::Zero)
     PCONV_CHECK(r0 >= r1 || (g_row0 + r0 >= 0 && g_row0 + r1 <= height),
                 "cpu_step: a non-zero border computes rows of the global image only");
-  switch (ch) {
-    case Channels::Grey: step_rows<1>(f, lay, src_frame, dst_frame, r0, r1, be, border, g_row0, height); break;
-    case Channels::Rgb: step_rows<3>(f, lay, src_frame, dst_frame, r0, r1, be, border, g_row0, height); break;
-    case Channels::Rgba: step_rows<4>(f, lay, src_frame, dst_frame, r0, r1, be, border, g_row0, height); break;
-  }
+  with_channels(ch, [&](auto chn) {
+    step_rows<decltype(chn)::value>(f, lay, src_frame, dst_frame, r0, r1, be, border, g_row0, height);
+  });
 }
 
 void cpu_fused_launch(const Filter& f, Channels ch, const FrameLayout& lay, const uint8_t* src_frame,
@@ -349,30 +360,10 @@ int configure_cpu_threads(int share) {
   return n;
 }
 
-void cpu_convolve(const Filter& f, const ImageGeom& geom, const uint8_t* in, uint8_t* out, int reps, CpuBackend be,
-                  int threads, Border border) {
-  geom.validate();
-  PCONV_CHECK(reps >= 0, "repetitions must be >= 0");
-  const int64_t rb = geom.row_bytes();
-  const FrameLayout lay = FrameLayout::make(rb, geom.height, 1);
-  std::vector<uint8_t> fa(static_cast<size_t>(lay.bytes()), 0), fb(static_cast<size_t>(lay.bytes()), 0);
-  for (int64_t r = 0; r < geom.height; ++r) std::memcpy(fa.data() + lay.offset(r), in + r * rb, rb);
-  const int saved = omp_get_max_threads();
-  if (be == CpuBackend::OpenMP && threads <= 0 && !std::getenv("OMP_NUM_THREADS")) threads = default_cpu_threads();
-  if (be == CpuBackend::OpenMP && threads > 0) omp_set_num_threads(threads);
-  uint8_t* src = fa.data();
-  uint8_t* dst = fb.data();
-  for (int t = 0; t < reps; ++t) {
-    cpu_step(f, geom.channels, lay, src, dst, 0, geom.height, be, border, 0, geom.height);
-    std::swap(src, dst);  // newest result is always in `src` (fixes SURVEY §A3)
-  }
-  if (be == CpuBackend::OpenMP && threads > 0) omp_set_num_threads(saved);
-  for (int64_t r = 0; r < geom.height; ++r) std::memcpy(out + r * rb, src + lay.offset(r), rb);
-}
-
 namespace {
 
-// OpenMP team of a whole-image call (cpu_convolve's rule), restored on exit.
+// OpenMP team of a whole-image call, restored on exit: `threads`, or
+// default_cpu_threads() when neither it nor OMP_NUM_THREADS says.
 struct TeamScope {
   int saved = omp_get_max_threads();
   bool set = false;
@@ -388,42 +379,85 @@ struct TeamScope {
 
 }  // namespace
 
+HostFrames::HostFrames(const Filter& f, const ImageGeom& geom, CpuBackend be, Border border)
+    : f_(f), geom_(geom), be_(be), border_(border) {
+  geom_.validate();
+  lay_ = FrameLayout::make(geom_.row_bytes(), geom_.height, 1);
+}
+
+void HostFrames::load(const std::function<void(uint8_t* row0, int64_t pitch)>& fill) {
+  cur_.assign(static_cast<size_t>(lay_.bytes()), 0);
+  nxt_.assign(static_cast<size_t>(lay_.bytes()), 0);
+  fill(cur_.data() + lay_.offset(0), lay_.pitch);
+}
+
+void HostFrames::load(const uint8_t* in) {
+  const int64_t rb = lay_.row_bytes;
+  load([&](uint8_t* row0, int64_t pitch) {
+    for (int64_t r = 0; r < geom_.height; ++r) std::memcpy(row0 + r * pitch, in + r * rb, static_cast<size_t>(rb));
+  });
+}
+
+void HostFrames::release() {
+  std::vector<uint8_t>().swap(cur_);
+  std::vector<uint8_t>().swap(nxt_);
+}
+
+void HostFrames::step() {
+  cpu_step(f_, geom_.channels, lay_, cur_.data(), nxt_.data(), 0, geom_.height, be_, border_, 0, geom_.height);
+  cur_.swap(nxt_);  // newest result is always in `cur_` (fixes SURVEY §A3)
+}
+
+uint64_t HostFrames::residual() const {
+  return cpu_residual(f_, geom_.channels, lay_, cur_.data(), 0, geom_.height, be_, border_, 0, geom_.height);
+}
+
+void HostFrames::copy_out(uint8_t* out) const {
+  const int64_t rb = lay_.row_bytes;
+  for (int64_t r = 0; r < geom_.height; ++r)
+    std::memcpy(out + r * rb, cur_.data() + lay_.offset(r), static_cast<size_t>(rb));
+}
+
+StableStats HostFrames::run_until_stable(int max_reps, int check_every) {
+  PCONV_CHECK(max_reps >= 0, "repetitions must be >= 0");
+  PCONV_CHECK(check_every >= 1, "check_every must be >= 1");
+  StableStats st;
+  do {
+    const int k = std::min(check_every, max_reps - st.reps_done);
+    for (int t = 0; t < k; ++t) step();
+    st.reps_done += k;
+    st.residual = residual();
+    ++st.checks;
+    st.converged = st.residual == 0;
+  } while (!st.converged && st.reps_done < max_reps);
+  return st;
+}
+
+void cpu_convolve(const Filter& f, const ImageGeom& geom, const uint8_t* in, uint8_t* out, int reps, CpuBackend be,
+                  int threads, Border border) {
+  HostFrames fr(f, geom, be, border);
+  PCONV_CHECK(reps >= 0, "repetitions must be >= 0");
+  fr.load(in);
+  TeamScope team(be, threads);
+  for (int t = 0; t < reps; ++t) fr.step();
+  fr.copy_out(out);
+}
+
 uint64_t cpu_image_residual(const Filter& f, const ImageGeom& geom, const uint8_t* in, CpuBackend be, int threads,
                             Border border) {
-  geom.validate();
-  const int64_t rb = geom.row_bytes();
-  const FrameLayout lay = FrameLayout::make(rb, geom.height, 1);
-  std::vector<uint8_t> fa(static_cast<size_t>(lay.bytes()), 0);
-  for (int64_t r = 0; r < geom.height; ++r) std::memcpy(fa.data() + lay.offset(r), in + r * rb, rb);
+  HostFrames fr(f, geom, be, border);
+  fr.load(in);
   TeamScope team(be, threads);
-  return cpu_residual(f, geom.channels, lay, fa.data(), 0, geom.height, be, border, 0, geom.height);
+  return fr.residual();
 }
 
 StableStats cpu_convolve_until_stable(const Filter& f, const ImageGeom& geom, const uint8_t* in, uint8_t* out,
                                       int max_reps, int check_every, CpuBackend be, int threads, Border border) {
-  geom.validate();
-  PCONV_CHECK(max_reps >= 0, "repetitions must be >= 0");
-  PCONV_CHECK(check_every >= 1, "check_every must be >= 1");
-  const int64_t rb = geom.row_bytes();
-  const FrameLayout lay = FrameLayout::make(rb, geom.height, 1);
-  std::vector<uint8_t> fa(static_cast<size_t>(lay.bytes()), 0), fb(static_cast<size_t>(lay.bytes()), 0);
-  for (int64_t r = 0; r < geom.height; ++r) std::memcpy(fa.data() + lay.offset(r), in + r * rb, rb);
+  HostFrames fr(f, geom, be, border);
+  fr.load(in);
   TeamScope team(be, threads);
-  uint8_t* src = fa.data();
-  uint8_t* dst = fb.data();
-  StableStats st;
-  do {
-    const int k = std::min(check_every, max_reps - st.reps_done);
-    for (int t = 0; t < k; ++t) {
-      cpu_step(f, geom.channels, lay, src, dst, 0, geom.height, be, border, 0, geom.height);
-      std::swap(src, dst);
-    }
-    st.reps_done += k;
-    st.residual = cpu_residual(f, geom.channels, lay, src, 0, geom.height, be, border, 0, geom.height);
-    ++st.checks;
-    st.converged = st.residual == 0;
-  } while (!st.converged && st.reps_done < max_reps);
-  for (int64_t r = 0; r < geom.height; ++r) std::memcpy(out + r * rb, src + lay.offset(r), rb);
+  const StableStats st = fr.run_until_stable(max_reps, check_every);
+  fr.copy_out(out);
   return st;
 }
 

@@ -353,6 +353,13 @@ bool BandEngine::refresh_halo() {
   return true;
 }
 
+void BandEngine::launch_band_residual() {
+  StencilLaunch a = make_launch(LaunchSpec{}, cur_);
+  a.r0 = 0;
+  a.r1 = band_.rows;
+  launch_residual(filter_, geom_.channels, a, reinterpret_cast<uint64_t*>(res_count_.data()), cs_);
+}
+
 void BandEngine::enqueue_residual() {
   TraceRange tr("pconv.residual");
   if (!res_count_.data()) {
@@ -366,12 +373,9 @@ void BandEngine::enqueue_residual() {
     res_ev_ = Event::create();
   }
   refresh_halo();
-  StencilLaunch a = make_launch(LaunchSpec{}, cur_);
-  a.r0 = 0;
-  a.r1 = band_.rows;
   // The device counter is never zeroed again: it runs on, a check is the
   // difference to the value the check before it read (the stream is in order).
-  launch_residual(filter_, geom_.channels, a, reinterpret_cast<uint64_t*>(res_count_.data()), cs_);
+  launch_band_residual();
   if (opt_.kernel_copies)
     launch_copy_rows(res_count_.data(), 16, res_host_.data(), 16, 16, 1, cs_);
   else
@@ -397,13 +401,10 @@ uint64_t BandEngine::residual() {
 
 std::vector<double> BandEngine::time_residual(int launches) {
   (void)residual();  // the counter exists, the ghost zone is valid
-  StencilLaunch a = make_launch(LaunchSpec{}, cur_);
-  a.r0 = 0;
-  a.r1 = band_.rows;
   std::vector<double> ms;
   for (int i = 0; i < launches; ++i) {
     ev_t0_.record(cs_);
-    launch_residual(filter_, geom_.channels, a, reinterpret_cast<uint64_t*>(res_count_.data()), cs_);
+    launch_band_residual();
     ev_t1_.record(cs_);
     PCONV_HIP_CHECK(hipStreamSynchronize(cs_));
     ms.push_back(Event::elapsed_ms(ev_t0_, ev_t1_));

@@ -379,6 +379,66 @@ void test_streamed_plan_cpu() {
       }
 }
 
+// HostFrames::run_until_stable against the same run spelled out with the
+// whole-image calls: chunks of K repetitions through cpu_convolve, a
+// cpu_image_residual after each; and cpu_convolve in place (out == in).
+void test_host_frames() {
+  const Filter neg = Filter::custom({3, 1, 0, 2, 5, 1, -1, 2, 4}, 17);
+  for (const ImageGeom& geo : {ImageGeom{37, 21, Channels::Rgb}, ImageGeom{13, 9, Channels::Grey}})
+    for (const Filter& f : {Filter::gaussian(), Filter::box(), neg})
+      for (Border border : {Border::Zero, Border::Replicate})
+        for (CpuBackend be : {CpuBackend::Serial, CpuBackend::OpenMP}) {
+          const auto img = random_bytes(static_cast<size_t>(geo.bytes()), static_cast<uint32_t>(geo.width));
+          for (int K : {1, 8})
+            for (int max : {0, 1, K - 1, K, 400}) {
+              StableStats want;
+              std::vector<uint8_t> x = img, y(img.size());
+              do {
+                const int k = std::min(K, max - want.reps_done);
+                cpu_convolve(f, geo, x.data(), y.data(), k, be, 3, border);
+                x.swap(y);
+                want.reps_done += k;
+                want.residual = cpu_image_residual(f, geo, x.data(), be, 3, border);
+                ++want.checks;
+                want.converged = want.residual == 0;
+              } while (!want.converged && want.reps_done < max);
+              HostFrames fr(f, geo, be, border);
+              fr.load(img.data());
+              const StableStats got = fr.run_until_stable(max, K);
+              std::vector<uint8_t> out(img.size(), 0xEE);
+              fr.copy_out(out.data());
+              const bool ok = got.reps_done == want.reps_done && got.residual == want.residual &&
+                              got.checks == want.checks && got.converged == want.converged && out == x &&
+                              fr.residual() == want.residual;
+              if (!ok)
+                std::fprintf(stderr, "host frames mismatch: %s %dx%d border=%s omp=%d K=%d max=%d\n", f.name.c_str(),
+                             static_cast<int>(geo.width), static_cast<int>(geo.height), border_name(border),
+                             be == CpuBackend::OpenMP, K, max);
+              EXPECT(ok);
+            }
+          // a frame filled through the callback holds the same image
+          HostFrames fr(f, geo, be, border);
+          fr.load([&](uint8_t* row0, int64_t pitch) {
+            for (int64_t r = 0; r < geo.height; ++r)
+              std::memcpy(row0 + r * pitch, img.data() + r * geo.row_bytes(), static_cast<size_t>(geo.row_bytes()));
+          });
+          std::vector<uint8_t> a(img.size()), b = img;
+          for (int t = 0; t < 3; ++t) fr.step();
+          fr.copy_out(a.data());
+          cpu_convolve(f, geo, b.data(), b.data(), 3, be, 3, border);  // out == in
+          std::vector<uint8_t> ref(img.size());
+          cpu_convolve(f, geo, img.data(), ref.data(), 3, be, 3, border);
+          EXPECT(b == ref);
+          EXPECT(a == ref);
+        }
+  EXPECT(throws([] {
+    HostFrames fr(Filter::gaussian(), ImageGeom{4, 4, Channels::Grey}, CpuBackend::Serial);
+    const std::vector<uint8_t> z(16, 0);
+    fr.load(z.data());
+    fr.run_until_stable(4, 0);
+  }));
+}
+
 }  // namespace
 
 int main() {
@@ -391,6 +451,7 @@ int main() {
   test_cli();
   test_cli_policy_flags();
   test_streamed_plan_cpu();
+  test_host_frames();
   std::printf("native tests: %d checks, %d failures\n", g_checks, g_failures);
   return g_failures ? 1 : 0;
 }

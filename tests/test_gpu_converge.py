@@ -58,21 +58,30 @@ def _fixed_point(pconv_mod, c, h, w, filt, border):
     return _FIX[key]
 
 
-def _count(native, frame_rows, rb, h, halo, filt, c, r0, r1, g_row0, height, border):
-    """The kernel's count on a frame given as (h + 2 halo, row_bytes) rows
-    (ghost rows included), after checking that it wrote nothing: the canaries
-    around the frame, the pad columns and the frame itself are unchanged."""
+def _canary_frame(native, frame_rows, rb, h, halo):
+    """A frame given as (h + 2 halo, row_bytes) rows (ghost rows included) on
+    the device, zero pad columns, canaries around it: the buffer, its layout
+    and the address of (row 0, column 0)."""
     import torch
 
     lay = native.frame_layout(rb, h, halo)
     full = np.zeros((h + 2 * halo, lay["pitch"]), np.uint8)
     full[:, 16:16 + rb] = frame_rows
-    src = torch.full((lay["bytes"] + 2 * GUARD,), CANARY, dtype=torch.uint8, device="cuda")
-    src[GUARD:GUARD + lay["bytes"]] = torch.from_numpy(full.reshape(-1)).cuda()
+    buf = torch.full((lay["bytes"] + 2 * GUARD,), CANARY, dtype=torch.uint8, device="cuda")
+    buf[GUARD:GUARD + lay["bytes"]] = torch.from_numpy(full.reshape(-1)).cuda()
+    return buf, lay, buf.data_ptr() + GUARD + lay["pitch"] * halo + 16
+
+
+def _count(native, frame_rows, rb, h, halo, filt, c, r0, r1, g_row0, height, border):
+    """The kernel's count on such a frame, after checking that it wrote
+    nothing: the canaries around the frame, the pad columns and the frame
+    itself are unchanged."""
+    import torch
+
+    src, lay, row0 = _canary_frame(native, frame_rows, rb, h, halo)
     before = src.cpu().numpy().copy()
-    base = lay["pitch"] * halo + 16
     torch.cuda.synchronize()
-    n = native.launch_residual(filt, NAME[c], src.data_ptr() + GUARD + base, lay["pitch"], rb, r0, r1, -halo, h + halo,
+    n = native.launch_residual(filt, NAME[c], row0, lay["pitch"], rb, r0, r1, -halo, h + halo,
                                g_row0, height, torch.cuda.current_stream().cuda_stream, border=border)
     torch.cuda.synchronize()
     after = src.cpu().numpy()
@@ -120,6 +129,50 @@ def test_kernel_count_equals_oracle(pconv_mod, native, filt, border):
                 if got != want:
                     bad.append((c, h, w, got, want))
     assert ran >= 60
+    assert not bad, (len(bad), bad[:12])
+
+
+def _step_changes(native, img, filt, c, variant):
+    """Bytes of [0, row_bytes) that one single-step launch_stencil changes
+    (zero border, one garbage ghost row either side as in _whole)."""
+    import torch
+
+    h, rb = img.shape[0], img.shape[1] * c
+    rows = np.full((h + 2, rb), 0xEE, np.uint8)
+    rows[1:1 + h] = img.reshape(h, rb)
+    src, lay, s0 = _canary_frame(native, rows, rb, h, 1)
+    dst, _, d0 = _canary_frame(native, np.zeros((h + 2, rb), np.uint8), rb, h, 1)
+    native.launch_stencil(filt, NAME[c], s0, d0, lay["pitch"], rb, 0, h, -1, h + 1, 1, 0, h,
+                          torch.cuda.current_stream().cuda_stream, variant)
+    torch.cuda.synchronize()
+    d = dst.cpu().numpy()
+    assert (d[:GUARD] == CANARY).all() and (d[-GUARD:] == CANARY).all(), "write outside the frame"
+    out = d[GUARD:GUARD + lay["bytes"]].reshape(h + 2, lay["pitch"])[1:1 + h, 16:16 + rb]
+    return int(np.count_nonzero(out != rows[1:1 + h]))
+
+
+@pytest.mark.parametrize("filt,variant", [("gaussian", "int9"), ("box", "float9"), ("neg", "float9")])
+def test_residual_counts_what_the_single_step_changes(pconv_mod, native, filt, variant):
+    """The two users of the nine-tap core agree: launch_residual's count is the
+    number of bytes k_generic9 changes, and both are the oracle's.  Row bytes
+    17, 31, 32, 33, 35, 36 end the row at different places of a lane's 24-byte
+    window (nearest whole pixels for 3 and 4 channels); 1029 crosses a
+    workgroup in x."""
+    pf, nf = _filters(pconv_mod, filt)
+    bad, ran = [], 0
+    for c in (1, 3, 4):
+        ws = sorted({max(1, round(rb / c)) for rb in (17, 31, 32, 33, 35, 36)} | ({1029} if c == 1 else set()))
+        if c == 1:
+            assert ws == [17, 31, 32, 33, 35, 36, 1029]
+        for w in ws:
+            for h in (1, 2, native.RESIDUAL_BLOCK_ROWS + 1):
+                img = _image(c, h, w)
+                got, want = _whole(native, pconv_mod, img, filt, "zero")
+                stepped = _step_changes(native, img, nf, c, variant)
+                ran += 1
+                if not got == stepped == want:
+                    bad.append((c, h, w, got, stepped, want))
+    assert ran == 3 * (7 + 4 + 3)
     assert not bad, (len(bad), bad[:12])
 
 
