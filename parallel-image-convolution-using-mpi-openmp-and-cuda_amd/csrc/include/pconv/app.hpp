@@ -22,7 +22,8 @@ namespace pconv {
 struct AppReport {
   double loop_s = 0;       // max over ranks of the rep-loop time
   double e2e_s = 0;        // end-to-end wall time (incl. I/O and device init)
-  double mpix_per_s = 0;   // W*H*reps / loop_s / 1e6
+  double mpix_per_s = 0;   // W*H*frames*reps / loop_s / 1e6
+  int frames = 1;          // --frames: images in the file, each convolved on its own
   int gpus = 1;
   int halo = 1, fuse = 1;
   int launches = 0, exchanges = 0;

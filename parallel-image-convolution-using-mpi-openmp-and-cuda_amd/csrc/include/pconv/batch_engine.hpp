@@ -1,0 +1,77 @@
+// Batch engine: up to `capacity` whole images of ONE geometry resident on one
+// GPU, advanced together — every launch carries StencilLaunch::batch = n, so a
+// run of `reps` repetitions is ceil(reps / fuse) launches whatever n.
+//
+// Small images cannot fill 256 CUs one at a time (a launch of the temporal
+// kernels costs its per-step latency, not its work: docs/PERFORMANCE.md §1.5);
+// a batch widens the grid instead of lengthening the queue of launches.
+//
+// No bands, neighbours or transport: each image is the band {y0 = 0, rows = H}
+// of BandEngine, and the plan is plan_band's for that band.  Out of scope here
+// (see docs/ARCHITECTURE.md §5): hipGraph capture, residual / run-until-stable,
+// images of different sizes, more than one GPU.
+#pragma once
+
+#include <hip/hip_runtime_api.h>
+
+#include "pconv/device.hpp"
+#include "pconv/engine.hpp"
+#include "pconv/filter.hpp"
+#include "pconv/image.hpp"
+#include "pconv/kernels.hpp"
+
+namespace pconv {
+
+class BatchEngine {
+ public:
+  // Options read: device, fuse, variant, border, compute_stream, timing,
+  // kernel_copies (the rest describe bands and pipelines).
+  BatchEngine(const ImageGeom& geom, const Filter& filter, int capacity, const EngineOptions& opt);
+  ~BatchEngine();
+
+  const ImageGeom& geom() const { return geom_; }
+  const FrameLayout& layout() const { return lay_; }
+  const EngineOptions& options() const { return opt_; }
+  int capacity() const { return capacity_; }
+  // Bytes between image b's and image b + 1's frame: a whole number of
+  // pitches >= the frame's bytes (a frame is whole pitches, so exactly that).
+  int64_t batch_stride() const { return stride_; }
+  hipStream_t compute_stream() const { return cs_; }
+  // Frame `which` (0/1) of image 0 at (row 0, data column 0); cur() = the newest.
+  uint8_t* frame_at(int which) const { return frame_[which & 1].data() + lay_.offset(0); }
+  int cur() const { return cur_; }
+
+  // Copy n <= capacity packed images (row pitch row_bytes, images back to
+  // back) into the current frames / the newest frames out.  Async on the
+  // compute stream; a host pointer should be pinned.  `device`: p is device
+  // memory.
+  void upload(const uint8_t* p, int n, bool device = false);
+  void download(uint8_t* p, int n, bool device = false);
+  // Enqueue `reps` repetitions of images [0, n) (async).
+  void run(int reps, int n);
+
+  void wait_stream(hipStream_t s);
+  void signal_stream(hipStream_t s);
+  void synchronize();
+  const RunStats& last_stats() const { return stats_; }
+
+ private:
+  void check_n(const char* who, int n) const;
+
+  ImageGeom geom_;
+  Filter filter_;
+  EngineOptions opt_;
+  int capacity_ = 0;
+  FrameLayout lay_;
+  int64_t stride_ = 0;
+  DeviceBuffer frame_[2];
+  int cur_ = 0;
+  Stream own_cs_;
+  hipStream_t cs_ = nullptr;
+  Event ev_t0_, ev_t1_, ev_sync_;
+  RunStats stats_;
+  double wall_t0_ = 0;
+  bool timing_pending_ = false;
+};
+
+}  // namespace pconv

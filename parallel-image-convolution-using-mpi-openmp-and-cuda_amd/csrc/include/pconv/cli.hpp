@@ -41,6 +41,10 @@ struct CliConfig {
   std::string out;  // "" = blur_<name>
   bool synthetic = false;
   uint64_t seed = 0;
+  // --frames N: the raw file holds N images back to back, each convolved on its
+  // own (hip: one BatchEngine on 1 GPU; cpu / omp: a loop over the frames);
+  // --synthetic makes frame k from seed + k.
+  int frames = 1;
   bool check = false;
   bool json = false;
   int threads = 0;

@@ -44,6 +44,13 @@ struct StencilLaunch {
   // kernels only (they apply it at every fused step): Auto routes every step
   // count to them, the single-step variants reject it.
   Border border = Border::Zero;
+  // Image batch (temporal kernels only): `batch` independent images of this
+  // geometry advance in the one launch.  Every other field describes ONE image
+  // and applies to each; image b's frame lies b * batch_stride bytes after
+  // image 0's, in src and dst alike (ignored when batch == 1).  Images never
+  // read each other's rows: the batch only moves the base pointers.
+  int batch = 1;
+  int64_t batch_stride = 0;
 };
 
 enum class KernelVariant : int {
@@ -148,8 +155,8 @@ void set_float_shape(int m, int nw);
 // Forget the tuned shapes: of both kernels, of the float kernel alone.
 void clear_swar_tuning();
 void clear_float_tuning();
-// Tuned SWAR entries: ({channels, steps, rows, row_bytes, step_form, kernel}, shape); kernel 0: the tile
-// kernel k_swar, 1: the buffer-op tile kernel k_swar_pf.
+// Tuned SWAR entries: ({channels, steps, rows, row_bytes, step_form, kernel, batch}, shape); kernel 0: the
+// tile kernel k_swar, 1: the buffer-op tile kernel k_swar_pf.
 std::vector<std::pair<std::vector<int64_t>, SwarShape>> swar_tuned();
 
 }  // namespace pconv

@@ -162,6 +162,7 @@ void launch_residual(const Filter& f, Channels ch, const StencilLaunch& a_in, ui
   if (a.r1 <= a.r0) return;
   // Geometry guards: every access of the launch must stay inside the frame.
   PCONV_CHECK(a.row_bytes >= 1, "launch_residual: empty rows");
+  PCONV_CHECK(a.batch == 1, "launch_residual: batch not supported (one image per launch)");
   check_frame_access("launch_residual", a, a.src && counter, 1);
   PCONV_CHECK(reinterpret_cast<uintptr_t>(a.src) % 16 == 0, "launch_residual: frame rows must be 16-byte aligned");
   PCONV_CHECK(a.row_bytes < (int64_t(1) << 31) - 2048 && a.r1 - a.frame_lo < (int64_t(1) << 31) - 64 &&

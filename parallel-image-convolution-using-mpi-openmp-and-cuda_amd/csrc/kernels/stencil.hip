@@ -244,12 +244,13 @@ namespace {
 // it (false: nothing is left), and Auto becomes a kernel.
 //   The single-step kernels take their boundary from the frame's zero pad: a
 // non-zero border runs on the temporal kernels for every step count (an
-// int_exact filter is bit-identical in the float kernel by definition).
+// int_exact filter is bit-identical in the float kernel by definition), and
+// so does an image batch: only the temporal kernels' grids carry one.
 bool resolve_launch(const Filter& f, StencilLaunch& a, KernelVariant& v) {
   a.r0 = std::max(a.r0, -a.g_row0);
   a.r1 = std::min(a.r1, a.height - a.g_row0);
   if (a.r1 <= a.r0) return false;
-  const bool fused = a.steps > 1 || a.border != Border::Zero;
+  const bool fused = a.steps > 1 || a.border != Border::Zero || a.batch > 1;
   if (v == KernelVariant::Auto)
     v = f.binomial121 ? (fused ? KernelVariant::Temporal : KernelVariant::Binomial)
                       : (fused ? KernelVariant::FloatTemporal
@@ -276,6 +277,10 @@ void launch_stencil(const Filter& f, Channels ch, const StencilLaunch& a_in, hip
   check_frame_access("launch_stencil", a, a.src && a.dst && a.src != a.dst, a.steps);
   PCONV_CHECK(a.row_bytes < (int64_t(1) << 31) && a.r1 - a.frame_lo < (int64_t(1) << 31),
               "launch_stencil: geometry exceeds 32-bit kernel indices");
+  check_batch("launch_stencil", a);
+  PCONV_CHECK(a.batch == 1 || v == KernelVariant::Temporal || v == KernelVariant::FloatTemporal,
+              "launch_stencil: batch not supported by kernel '" + std::string(kernel_variant_name(v)) +
+                  "' (temporal and float_temporal only)");
   PCONV_CHECK(a.border == Border::Zero || v == KernelVariant::Temporal || v == KernelVariant::FloatTemporal,
               "launch_stencil: border '" + std::string(border_name(a.border)) + "' not supported by kernel '" +
                   std::string(kernel_variant_name(v)) + "' (temporal and float_temporal only)");

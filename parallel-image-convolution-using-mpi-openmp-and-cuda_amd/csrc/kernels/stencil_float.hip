@@ -266,8 +266,16 @@ __device__ __forceinline__ void ft_steps(u32 (&D)[M][2], uint2 (&lds)[2][NW][2][
 template <int CH, bool UNIFORM, int M, int NW, bool REP = false>
 __global__ __launch_bounds__(64 * NW) void k_float_temporal(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
                                                             int64_t pitch, int row_bytes, int r0, int r1, int steps,
-                                                            int g_row0, int height, FloatTaps tp) {
+                                                            int g_row0, int height, FloatTaps tp,
+                                                            int64_t batch_stride) {
   __shared__ uint2 lds[2][NW][2][64];  // [parity][wave][top/bottom][lane]
+  // Image of the batch: grid.z (scalar); it only moves the two base pointers.
+  // The empty asm settles both sums here, in scalar registers: from this line
+  // on the kernel holds what the single-image kernel held (two pointers), and
+  // the compiler allocates the registers of everything below as it did then.
+  src += static_cast<int64_t>(blockIdx.z) * batch_stride;
+  dst += static_cast<int64_t>(blockIdx.z) * batch_stride;
+  asm volatile("" : "+s"(src), "+s"(dst));
   const int lane = threadIdx.x & 63;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int hl = (steps * CH + 7) >> 3;  // halo lanes per side
@@ -424,9 +432,10 @@ struct FtGeom {
   int vlanes = 0;   // valid 8-byte output chunks per strip
   int vrows = 0;    // valid output rows per tile
   int64_t col_tiles = 0, row_tiles = 0;
+  int64_t tiles = 0;  // workgroups: col_tiles x row_tiles x batch (grid.z)
 };
 
-FtGeom ft_geom(const FloatShape& sh, int ch, int steps, int64_t rows, int64_t row_bytes) {
+FtGeom ft_geom(const FloatShape& sh, int ch, int steps, int64_t rows, int64_t row_bytes, int batch = 1) {
   FtGeom g;
   g.hl = (steps * ch + 7) / 8;
   g.vlanes = 64 - 2 * g.hl;
@@ -435,6 +444,7 @@ FtGeom ft_geom(const FloatShape& sh, int ch, int steps, int64_t rows, int64_t ro
   if (!g.ok) return g;
   g.col_tiles = ceil_div<int64_t>(ceil_div<int64_t>(row_bytes, 8), g.vlanes);
   g.row_tiles = ceil_div<int64_t>(rows, g.vrows);
+  g.tiles = g.col_tiles * g.row_tiles * batch;
   return g;
 }
 
@@ -447,7 +457,7 @@ FtGeom ft_geom(const FloatShape& sh, int ch, int steps, int64_t rows, int64_t ro
 // 16x8 (best).  set_float_shape(M, NW) forces one.
 std::atomic<int> g_ft_force_m{0}, g_ft_force_nw{0};
 
-FloatShape pick_ft_shape(int steps, int ch, int64_t rows, int64_t row_bytes) {
+FloatShape pick_ft_shape(int steps, int ch, int64_t rows, int64_t row_bytes, int batch = 1) {
   if (const int fm = g_ft_force_m.load(std::memory_order_relaxed)) {
     const size_t i = ft_shape_index(fm, g_ft_force_nw.load(std::memory_order_relaxed));
     if (i < kNumFtShapes) return kFtShapes[i];
@@ -462,9 +472,9 @@ FloatShape pick_ft_shape(int steps, int ch, int64_t rows, int64_t row_bytes) {
   FloatShape most = kFtShapes[kNumFtShapes - 1];  // the smallest tile
   int64_t most_wgs = -1;
   for (const auto& c : kFtShapes) {
-    const FtGeom g = ft_geom(c, ch, steps, rows, row_bytes);
+    const FtGeom g = ft_geom(c, ch, steps, rows, row_bytes, batch);
     if (!g.ok) continue;
-    const int64_t wgs = g.col_tiles * g.row_tiles;
+    const int64_t wgs = g.tiles;
     const int64_t rounds = ceil_div<int64_t>(wgs, cus);
     if (4 * wgs >= 3 * static_cast<int64_t>(cus) && 4 * wgs >= 3 * rounds * cus) return c;
     if (wgs > most_wgs) {
@@ -477,14 +487,17 @@ FloatShape pick_ft_shape(int steps, int ch, int64_t rows, int64_t row_bytes) {
 
 template <int CH, bool UNIFORM, int M, int NW>
 void launch_ft_shape(const StencilLaunch& a, const FloatTaps& tp, hipStream_t s) {
-  const FtGeom g = ft_geom(FloatShape{M, NW}, CH, a.steps, a.r1 - a.r0, a.row_bytes);
+  const FtGeom g = ft_geom(FloatShape{M, NW}, CH, a.steps, a.r1 - a.r0, a.row_bytes, a.batch);
   PCONV_CHECK(g.ok, "float temporal kernel: steps too large for the tile");
-  const dim3 grid(static_cast<unsigned>(g.col_tiles), static_cast<unsigned>(g.row_tiles));
+  PCONV_CHECK(g.tiles < (int64_t(1) << 31), "float temporal kernel: too many tiles (batch x tiles per image)");
+  const dim3 grid(static_cast<unsigned>(g.col_tiles), static_cast<unsigned>(g.row_tiles),
+                  static_cast<unsigned>(a.batch));
   const auto kern = a.border == Border::Replicate ? &k_float_temporal<CH, UNIFORM, M, NW, true>
                                                   : &k_float_temporal<CH, UNIFORM, M, NW, false>;
   kern<<<grid, dim3(64 * NW), 0, s>>>(
       a.src, a.dst, a.pitch, static_cast<int>(a.row_bytes), static_cast<int>(a.r0), static_cast<int>(a.r1), a.steps,
-      static_cast<int>(a.g_row0), static_cast<int>(std::min<int64_t>(a.height, int64_t(1) << 30)), tp);
+      static_cast<int>(a.g_row0), static_cast<int>(std::min<int64_t>(a.height, int64_t(1) << 30)), tp,
+      a.batch > 1 ? a.batch_stride : int64_t(0));
 }
 
 template <int CH, bool UNIFORM>
@@ -499,7 +512,7 @@ void launch_ft_with(const StencilLaunch& a, const FloatTaps& tp, hipStream_t s, 
 // Empirical shape tuning, as for the SWAR kernel (stencil_swar.hip): on the
 // first launch of a geometry every shape that runs it is timed on the REAL
 // launch (fastest_candidate, tuning.hpp) and the fastest is cached per
-// (channels, uniform, steps, rows, row bytes).  The
+// (channels, uniform, steps, rows, row bytes, batch).  The
 // shape is a large lever on these small frames and not monotonic in the
 // model (1920x2520 RGB box, 4 steps: 8.0 us/rep with 16x8 tiles, 9.2-10.4
 // with the others; gpurun_out/r03/g/float_sweep.jsonl).  Never while the
@@ -509,8 +522,10 @@ struct FtKey {
   bool uniform;
   int steps;
   int64_t rows, row_bytes;
+  int batch;
   bool operator<(const FtKey& o) const {
-    return std::tie(ch, uniform, steps, rows, row_bytes) < std::tie(o.ch, o.uniform, o.steps, o.rows, o.row_bytes);
+    return std::tie(ch, uniform, steps, rows, row_bytes, batch) <
+           std::tie(o.ch, o.uniform, o.steps, o.rows, o.row_bytes, o.batch);
   }
 };
 std::mutex g_ft_mu;
@@ -519,9 +534,9 @@ std::map<FtKey, FloatShape> g_ft_tuned;
 template <int CH, bool UNIFORM>
 FloatShape tuned_ft_shape(const StencilLaunch& a, const FloatTaps& tp, hipStream_t s) {
   const int64_t rows = a.r1 - a.r0;
-  const FloatShape model = pick_ft_shape(a.steps, CH, rows, a.row_bytes);
+  const FloatShape model = pick_ft_shape(a.steps, CH, rows, a.row_bytes, a.batch);
   if (g_ft_force_m.load(std::memory_order_relaxed) || !shape_tuning_enabled()) return model;
-  const FtKey key{CH, UNIFORM, a.steps, rows, a.row_bytes};
+  const FtKey key{CH, UNIFORM, a.steps, rows, a.row_bytes, a.batch};
   {
     std::lock_guard<std::mutex> lk(g_ft_mu);
     auto it = g_ft_tuned.find(key);
@@ -549,6 +564,8 @@ void float_temporal(const Filter& f, Channels ch, const StencilLaunch& a, hipStr
   PCONV_CHECK(a.steps >= 1 && a.steps <= kMaxFusedSteps, "float temporal kernel: steps out of range");
   PCONV_CHECK(a.height < (int64_t(1) << 30) && a.g_row0 < (int64_t(1) << 30), "float temporal kernel: rows exceed 2^30");
   PCONV_CHECK(a.row_bytes > 0 && a.row_bytes < (int64_t(1) << 30), "float temporal kernel: row bytes out of range");
+  check_batch("launch_float_temporal", a);
+  PCONV_CHECK(a.batch <= 65535, "launch_float_temporal: batch " + std::to_string(a.batch) + " exceeds grid.z (65535)");
   FloatTaps tp;
   bool uniform = true;
   for (int i = 0; i < 9; ++i) {

@@ -116,7 +116,8 @@ template <int CH, int LW, int M, int NW, int FORM, bool REP = false>
 __global__ __launch_bounds__(64 * NW) void k_swar(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
                                                   int64_t pitch, int row_bytes, int r0, int r1,
                                                   int steps, int g_row0, int height, int nstrips, int pair_stride,
-                                                  int row_tiles, int xcd_swizzle) {
+                                                  int row_tiles, int xcd_swizzle, int tiles_per_image,
+                                                  int64_t batch_stride) {
   constexpr int NP = LW;       // pairs per row per lane
   constexpr int NQ = NP / 4;   // uint4 per row per lane
   using CT = typename Chunk<NP>::T;
@@ -126,16 +127,25 @@ __global__ __launch_bounds__(64 * NW) void k_swar(const uint8_t* __restrict__ sr
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int hl = (steps * CH + LW - 1) / LW;  // halo lanes per side
   const int vbytes = (64 - 2 * hl) * LW;      // valid output bytes per strip
-  // 1-D grid of pair_stride x row_tiles workgroups.  The dispatcher deals
-  // consecutive workgroup ids round-robin to the 8 XCDs; with xcd_swizzle the
-  // ids are remapped (bijectively) so that each XCD receives one contiguous
-  // run of tiles, walked down a column strip: vertically adjacent tiles,
-  // which read each other's halo rows, share an L2.
+  // 1-D grid of batch x pair_stride x row_tiles workgroups.  The dispatcher
+  // deals consecutive workgroup ids round-robin to the 8 XCDs; with
+  // xcd_swizzle the ids are remapped (bijectively) so that each XCD receives
+  // one contiguous run of tiles, walked down a column strip: vertically
+  // adjacent tiles, which read each other's halo rows, share an L2.  The
+  // remap covers the whole batch, so an XCD's run is whole neighbouring
+  // images; the image index is scalar (workgroup-uniform) and only moves the
+  // two base pointers.
   int tile = static_cast<int>(blockIdx.x);
   if (xcd_swizzle) {
     const int nwg = static_cast<int>(gridDim.x);
     const int q = nwg >> 3, rem = nwg & 7, xcd = tile & 7, local = tile >> 3;
     tile = xcd * q + min(xcd, rem) + local;
+  }
+  {
+    const int img = tile / tiles_per_image;
+    tile -= img * tiles_per_image;
+    src += static_cast<int64_t>(img) * batch_stride;
+    dst += static_cast<int64_t>(img) * batch_stride;
   }
   const int col = tile / row_tiles, rtile = tile - col * row_tiles;
   const int sA = col, sB = col + pair_stride;
@@ -218,7 +228,8 @@ template <int CH, int M, int NW, int FORM, bool REP = false>
 __global__ __launch_bounds__(64 * NW) void k_swar_pf(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
                                                      int pitch, int row_bytes, int r0, int r1,
                                                      int steps, int g_row0, int height, int nstrips, int pair_stride,
-                                                     int row_tiles, int xcd_swizzle) {
+                                                     int row_tiles, int xcd_swizzle, int tiles_per_image,
+                                                     int64_t batch_stride) {
   constexpr int LW = 4, NP = 4, NQ = 1;
   constexpr u32 kOut = 0x80000000u;  // offset past every descriptor's range
   __shared__ uint4 lds[2][NW][2][NQ][64];
@@ -230,19 +241,26 @@ __global__ __launch_bounds__(64 * NW) void k_swar_pf(const uint8_t* __restrict__
   // Source rows [lo_ok, hi_ok) are readable; destination rows [r0, st_end).
   const int lo_ok = max(r0 - steps, -g_row0), hi_ok = min(r1 + steps, height - g_row0);
   const int st_end = min(r1, height - g_row0);
-  const auto srsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<uint8_t*>(src) + static_cast<int64_t>(lo_ok) * pitch, 0, max(hi_ok - lo_ok, 0) * pitch, 0x00020000);
-  const auto drsrc = __builtin_amdgcn_make_buffer_rsrc(dst + static_cast<int64_t>(r0) * pitch, 0,
-                                                       max(st_end - r0, 0) * pitch, 0x00020000);
-  // XCD-aware tile order (as k_swar): each XCD gets one contiguous run of
-  // tiles walked down a column strip, so vertically adjacent tiles (which
-  // read each other's halo rows) share an L2.
+  // XCD-aware tile order over the whole batch (as k_swar): each XCD gets one
+  // contiguous run of tiles walked down a column strip, so vertically adjacent
+  // tiles (which read each other's halo rows) share an L2.  The image's own
+  // base goes into the descriptors: their < 2 GiB ranges are per image.
   int tile = static_cast<int>(blockIdx.x);
   if (xcd_swizzle) {
     const int nwg = static_cast<int>(gridDim.x);
     const int q = nwg >> 3, rem = nwg & 7, xcd = tile & 7, local = tile >> 3;
     tile = xcd * q + min(xcd, rem) + local;
   }
+  {
+    const int img = tile / tiles_per_image;
+    tile -= img * tiles_per_image;
+    src += static_cast<int64_t>(img) * batch_stride;
+    dst += static_cast<int64_t>(img) * batch_stride;
+  }
+  const auto srsrc = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<uint8_t*>(src) + static_cast<int64_t>(lo_ok) * pitch, 0, max(hi_ok - lo_ok, 0) * pitch, 0x00020000);
+  const auto drsrc = __builtin_amdgcn_make_buffer_rsrc(dst + static_cast<int64_t>(r0) * pitch, 0,
+                                                       max(st_end - r0, 0) * pitch, 0x00020000);
   const int col = tile / row_tiles, rtile = tile - col * row_tiles;
   const int sB = col + pair_stride;
   const int baseA = col * vbytes - hl * LW, baseB = sB * vbytes - hl * LW;
@@ -382,10 +400,11 @@ struct SwarGeom {
   int vbytes = 0;   // valid output bytes per strip
   int vrows = 0;    // valid output rows per tile
   int64_t nstrips = 0, pair_stride = 0, row_tiles = 0;
-  int64_t tiles = 0;  // workgroups, pair_stride x row_tiles; > 0: the shape runs the launch
+  int64_t tiles_per_image = 0;  // pair_stride x row_tiles
+  int64_t tiles = 0;  // workgroups, batch x tiles_per_image; > 0: the shape runs the launch
 };
 
-SwarGeom swar_geom(const SwarShape& sh, int ch, int steps, int64_t rows, int64_t row_bytes) {
+SwarGeom swar_geom(const SwarShape& sh, int ch, int steps, int64_t rows, int64_t row_bytes, int batch = 1) {
   SwarGeom g;
   g.hl = (steps * ch + sh.lw - 1) / sh.lw;
   g.vbytes = (64 - 2 * g.hl) * sh.lw;
@@ -395,7 +414,8 @@ SwarGeom swar_geom(const SwarShape& sh, int ch, int steps, int64_t rows, int64_t
   g.nstrips = ceil_div<int64_t>(row_bytes, g.vbytes);
   g.pair_stride = (g.nstrips + 1) / 2;
   g.row_tiles = ceil_div<int64_t>(rows, g.vrows);
-  g.tiles = g.pair_stride * g.row_tiles;
+  g.tiles_per_image = g.pair_stride * g.row_tiles;
+  g.tiles = g.tiles_per_image * batch;
   return g;
 }
 
@@ -411,18 +431,19 @@ template <int CH, size_t I, bool PF>
 void launch_tile(const StencilLaunch& a, hipStream_t s, int form) {
   constexpr SwarShape S = kTiles[I].shape;
   const char* who = PF ? "swar prefetch kernel" : "swar temporal kernel";
-  const SwarGeom g = swar_geom(S, CH, a.steps, a.r1 - a.r0, a.row_bytes);
+  const SwarGeom g = swar_geom(S, CH, a.steps, a.r1 - a.r0, a.row_bytes, a.batch);
   PCONV_CHECK(g.ok, std::string(who) + ": steps too large for the tile");
   if constexpr (PF)
     PCONV_CHECK(pf_launch_ok(a, a.steps), std::string(who) + ": needs whole dwords per row and < 2 GiB ranges");
-  PCONV_CHECK(g.tiles < (int64_t(1) << 31), std::string(who) + ": too many tiles");
+  PCONV_CHECK(g.tiles < (int64_t(1) << 31), std::string(who) + ": too many tiles (batch x tiles per image)");
   const dim3 grid(static_cast<unsigned>(g.tiles)), block(64 * S.nw);
   const int hmax = static_cast<int>(std::min<int64_t>(a.height, int64_t(1) << 30));
   const auto launch = [&](auto kern, auto pitch) {
     kern<<<grid, block, 0, s>>>(a.src, a.dst, pitch, static_cast<int>(a.row_bytes), static_cast<int>(a.r0),
                                 static_cast<int>(a.r1), a.steps, static_cast<int>(a.g_row0), hmax,
                                 static_cast<int>(g.nstrips), static_cast<int>(g.pair_stride),
-                                static_cast<int>(g.row_tiles), xcd_swizzle_enabled() ? 1 : 0);
+                                static_cast<int>(g.row_tiles), xcd_swizzle_enabled() ? 1 : 0,
+                                static_cast<int>(g.tiles_per_image), a.batch > 1 ? a.batch_stride : int64_t(0));
   };
   if constexpr (PF)
     launch(swar_pf_kernel<CH, S.m, S.nw>(form, a.border), static_cast<int>(a.pitch));
@@ -540,10 +561,10 @@ SwarResources swar_resources(SwarShape s, int ch) {
 // 4 image sizes, grey/RGB and 1-8-way bands (profiles/r01/band_shape_sweep.txt;
 // tools/fit_swar_data.py + tools/fit_swar_model.py); they pick the measured
 // best shape in 6 of 6 configurations of the current kernel.
-double swar_launch_cycles(SwarShape s, int steps, int ch, int64_t rows, int64_t row_bytes) {
+double swar_launch_cycles(SwarShape s, int steps, int ch, int64_t rows, int64_t row_bytes, int batch) {
   constexpr double kCyclesMin = 2.88, kCyclesOneWave = 5.86, kStep = 549.0, kRowLoad = 568.0, kLaunch = 17813.0;
   const int np = s.lw;
-  const SwarGeom geom = swar_geom(s, ch, steps, rows, row_bytes);
+  const SwarGeom geom = swar_geom(s, ch, steps, rows, row_bytes, batch);
   if (!geom.ok) return 1e300;
   const double g = static_cast<double>(geom.tiles);
   const KernelRes res = kernel_res(s, ch, default_form());
@@ -559,16 +580,27 @@ double swar_launch_cycles(SwarShape s, int steps, int ch, int64_t rows, int64_t 
   const double cross = 1.6 * ch;
   const double stage = (s.m + 2) * (2.0 * np + cross) + s.m * 4.0 * np + 24.0;
   const double instr = steps * stage + 40.0 + 3.0 * s.m * np;
-  const double round_cycles = instr * std::max(k * kCyclesMin, kCyclesOneWave) + steps * kStep + kRowLoad * s.m;
-  return rounds * round_cycles + kLaunch;
+  const auto round_cycles = [&](double waves) {
+    return instr * std::max(waves * kCyclesMin, kCyclesOneWave) + steps * kStep + kRowLoad * s.m;
+  };
+  // One image: every round of a CU at the occupancy of its fullest one — the
+  // form the constants were fitted in (tests/golden/swar_model.json).
+  if (batch == 1) return rounds * round_cycles(k) + kLaunch;
+  // A batch: the last, partial round at its own occupancy.  Charged like a
+  // full one, a batch whose images each leave a round partly empty and that
+  // needs one round more than they do would cost more than its images launched
+  // one by one (1920x2520 RGB at 8 steps, tile {4,16,4}: 3 of 4 workgroup slots
+  // per CU; two images: 144195 cycles against 2 x 68576), which no grid does.
+  const double full = std::floor(per_cu / L), rest = per_cu - full * L;
+  return full * round_cycles(L * s.nw / 4.0) + (rest > 0 ? round_cycles(rest * s.nw / 4.0) : 0.0) + kLaunch;
 }
 
-SwarShape pick_swar_shape(int steps, int ch, int64_t rows, int64_t row_bytes) {
+SwarShape pick_swar_shape(int steps, int ch, int64_t rows, int64_t row_bytes, int batch) {
   SwarShape best{0, 0, 0};
   if (override_shape(best) && swar_geom(best, ch, steps, rows, row_bytes).ok) return best;
   double best_cost = 1e300;
   for (const auto& t : kTiles) {
-    const double cost = swar_launch_cycles(t.shape, steps, ch, rows, row_bytes);
+    const double cost = swar_launch_cycles(t.shape, steps, ch, rows, row_bytes, batch);
     if (cost < best_cost) {
       best_cost = cost;
       best = t.shape;
@@ -604,14 +636,15 @@ void launch_choice(const StencilLaunch& a, Channels ch, hipStream_t stream, Swar
 
 // Empirical tuning: the model ranks the shapes, the best few are timed in both
 // step forms on the actual launch (fastest_candidate, tuning.hpp) and the
-// fastest (shape, form) is cached per (channels, steps, rows, row bytes).
+// fastest (shape, form) is cached per (channels, steps, rows, row bytes, batch).
 // Never while the stream is being captured into a graph (the engine tunes a
 // step's launches first).
 struct TuneKey {
   int ch, steps;
   int64_t rows, row_bytes;
+  int batch;
   bool operator<(const TuneKey& o) const {
-    return std::tie(ch, steps, rows, row_bytes) < std::tie(o.ch, o.steps, o.rows, o.row_bytes);
+    return std::tie(ch, steps, rows, row_bytes, batch) < std::tie(o.ch, o.steps, o.rows, o.row_bytes, o.batch);
   }
 };
 std::mutex g_tune_mu;
@@ -641,14 +674,14 @@ SwarChoice tuned_choice(const StencilLaunch& a, Channels ch, hipStream_t stream,
       fallback.kern = 1;
       return fallback;
     }
-    fallback.shape = pick_swar_shape(a.steps, c, rows, a.row_bytes);
+    fallback.shape = pick_swar_shape(a.steps, c, rows, a.row_bytes, a.batch);
     return fallback;
   }
   if (override_shape(fallback.shape) || !shape_tuning_enabled()) {
-    if (!override_shape(fallback.shape)) fallback.shape = pick_swar_shape(a.steps, c, rows, a.row_bytes);
+    if (!override_shape(fallback.shape)) fallback.shape = pick_swar_shape(a.steps, c, rows, a.row_bytes, a.batch);
     return fallback;
   }
-  const TuneKey key{c, a.steps, rows, a.row_bytes};
+  const TuneKey key{c, a.steps, rows, a.row_bytes, a.batch};
   {
     std::lock_guard<std::mutex> lk(g_tune_mu);
     auto it = g_tuned.find(key);
@@ -658,11 +691,11 @@ SwarChoice tuned_choice(const StencilLaunch& a, Channels ch, hipStream_t stream,
       return r;
     }
   }
-  fallback.shape = pick_swar_shape(a.steps, c, rows, a.row_bytes);
+  fallback.shape = pick_swar_shape(a.steps, c, rows, a.row_bytes, a.batch);
   if (!may_measure || stream_capturing(stream)) return fallback;
   std::vector<std::pair<double, SwarShape>> ranked;
   for (const auto& t : kTiles) {
-    const double cost = swar_launch_cycles(t.shape, a.steps, c, rows, a.row_bytes);
+    const double cost = swar_launch_cycles(t.shape, a.steps, c, rows, a.row_bytes, a.batch);
     if (cost < 1e299) ranked.emplace_back(cost, t.shape);
   }
   PCONV_CHECK(!ranked.empty(), "swar temporal kernel: steps too large for every tile shape");
@@ -715,7 +748,7 @@ std::vector<std::pair<std::vector<int64_t>, SwarShape>> swar_tuned() {
   std::vector<std::pair<std::vector<int64_t>, SwarShape>> out;
   for (const auto& kv : g_tuned)
     out.push_back({{kv.first.ch, kv.first.steps, kv.first.rows, kv.first.row_bytes, kv.second.form,
-                    kv.second.kern},
+                    kv.second.kern, kv.first.batch},
                    kv.second.shape});
   return out;
 }

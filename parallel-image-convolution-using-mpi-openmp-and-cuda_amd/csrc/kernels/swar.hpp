@@ -7,9 +7,10 @@
 
 namespace pconv {
 
-// Latency model of one launch (cycles) and the shape it picks.
-double swar_launch_cycles(SwarShape s, int steps, int ch, int64_t rows, int64_t row_bytes);
-SwarShape pick_swar_shape(int steps, int ch, int64_t rows, int64_t row_bytes);
+// Latency model of one launch (cycles) and the shape it picks; the grid is
+// `batch` images of rows x row_bytes (StencilLaunch::batch).
+double swar_launch_cycles(SwarShape s, int steps, int ch, int64_t rows, int64_t row_bytes, int batch = 1);
+SwarShape pick_swar_shape(int steps, int ch, int64_t rows, int64_t row_bytes, int batch = 1);
 
 // Enqueue the fused gaussian for `a.steps` repetitions.  Shape: forced
 // (set_swar_shape), else tuned on first use (the model's best candidates

@@ -10,8 +10,11 @@
 #include <utility>
 #include <vector>
 
+#include <string>
+
 #include "pconv/common.hpp"
 #include "pconv/device.hpp"
+#include "pconv/kernels.hpp"
 
 namespace pconv {
 
@@ -44,6 +47,18 @@ bool with_index(size_t i, F&& f) {
 inline bool stream_capturing(hipStream_t s) {
   hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
   return hipStreamIsCapturing(s, &st) == hipSuccess && st != hipStreamCaptureStatusNone;
+}
+
+// Guards of an image batch (StencilLaunch::batch), shared by the launches that
+// take one: the frames of a batch lie at a 16-byte aligned stride that holds a
+// whole frame, so no two images' frames overlap.
+inline void check_batch(const std::string& who, const StencilLaunch& a) {
+  PCONV_CHECK(a.batch >= 1, who + ": batch must be >= 1");
+  if (a.batch == 1) return;
+  PCONV_CHECK(a.batch_stride % 16 == 0, who + ": batch_stride must be a multiple of 16");
+  PCONV_CHECK(a.batch_stride >= (a.frame_hi - a.frame_lo) * a.pitch,
+              who + ": batch_stride " + std::to_string(a.batch_stride) + " is smaller than a frame (" +
+                  std::to_string((a.frame_hi - a.frame_lo) * a.pitch) + " bytes): frames would overlap");
 }
 
 constexpr int kTuneRepeats = 3;

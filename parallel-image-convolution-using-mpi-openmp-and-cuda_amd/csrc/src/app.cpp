@@ -19,6 +19,7 @@
 #include <sstream>
 #include <thread>
 
+#include "pconv/batch_engine.hpp"
 #include "pconv/cpu_stencil.hpp"
 #include "pconv/device.hpp"
 #include "pconv/engine.hpp"
@@ -432,6 +433,119 @@ AppReport run_gpu1(const CliConfig& c, JobCache* cache) {
   r.copies = eng.options().kernel_copies ? "kernel" : "sdma";
   if (c.check) r.mismatches = compare_with_oracle(c, g, host, r.reps_done);
   r.since_exec_s = seconds_since_exec();
+  return r;
+}
+
+// ------------------------------------------------------------ N frames
+// `--frames N`: the file holds N images of one geometry back to back, each
+// convolved on its own; the output has the same layout.  As far as file I/O
+// goes that is ONE image of N x height rows, so the size check, the read and
+// the write are the single image's.  hip: one BatchEngine on one GPU, every
+// launch carrying all N frames, through one full pinned buffer (the path
+// --check takes for a single image; no ring staging).  cpu / omp: one
+// HostFrames, loaded with each frame in turn.
+AppReport run_frames(const CliConfig& c) {
+  AppReport r;
+  const double t0 = wall_seconds();
+  PhaseClock pc(&r.phases);
+  const ImageGeom g = geom_of(c);
+  ImageGeom tall = g;
+  tall.height = g.height * c.frames;
+  tall.validate();
+  if (!c.synthetic) validate_input_file(c.image, tall);
+  const Filter f = Filter::by_name(c.filter);
+  const int64_t rb = g.row_bytes(), fb = g.bytes();
+  const auto load_frames = [&](uint8_t* dst) {
+    if (!c.synthetic) return read_rows(c.image, tall, 0, tall.height, dst, rb);
+    for (int k = 0; k < c.frames; ++k) synth_rows(g, c.seed + static_cast<uint64_t>(k), 0, g.height, dst + k * fb, rb);
+  };
+  r.frames = c.frames;
+  r.output = out_path(c);
+  const bool hip = c.backend == Backend::Hip;
+  PinnedBuffer pinned;
+  std::vector<uint8_t> pageable;
+  uint8_t* host = nullptr;
+  if (hip) {
+    set_device(0);
+    PCONV_HIP_CHECK(hipFree(nullptr));
+    pc.mark("hip_init");
+    pinned = PinnedBuffer(static_cast<size_t>(tall.bytes()));
+    host = pinned.data();
+    pc.mark("pinned_alloc");
+  } else {
+    pageable.resize(static_cast<size_t>(tall.bytes()));
+    host = pageable.data();
+  }
+  load_frames(host);
+  pc.mark(c.synthetic ? "synthesize" : "read");
+  if (hip) {
+    // One-shot process: the model's tile shape unless --tune on (run_gpu1).
+    struct TuneScope {
+      bool prev;
+      ~TuneScope() { (void)set_shape_tuning(prev); }
+    } tune_scope{set_shape_tuning(c.tune == 1)};
+    EngineOptions o = engine_options(c, g, 1, 0);
+    o.kernel_copies = c.copies != 0;
+    BatchEngine eng(g, f, c.frames, o);
+    pc.mark("device_alloc");
+    const int fz = std::max(1, eng.options().fuse);
+    const int warm_reps = c.reps <= 2 * fz ? c.reps : fz + c.reps % fz;
+    for (int i = 0; i < c.warmup; ++i) eng.run(warm_reps, c.frames);  // zero frames stay zero
+    if (c.warmup > 0) {
+      eng.synchronize();
+      pc.mark("warmup");
+    }
+    eng.upload(host, c.frames);
+    eng.synchronize();
+    pc.mark("h2d");
+    const double l0 = wall_seconds();
+    eng.run(c.reps, c.frames);
+    eng.synchronize();
+    r.loop_s = wall_seconds() - l0;
+    r.launches = eng.last_stats().launches;
+    pc.mark("loop");
+    eng.download(host, c.frames);
+    eng.synchronize();
+    pc.mark("d2h");
+    r.halo = static_cast<int>(eng.layout().halo);
+    r.fuse = eng.options().fuse;
+    r.kernel = kernel_variant_name(eng.options().variant);
+    r.copies = eng.options().kernel_copies ? "kernel" : "sdma";
+  } else {
+    const CpuBackend be = c.backend == Backend::Omp ? CpuBackend::OpenMP : CpuBackend::Serial;
+    r.kernel = be == CpuBackend::OpenMP ? "cpu-omp" : "cpu-serial";
+    HostFrames fr(f, g, be, c.border);
+    if (be == CpuBackend::OpenMP) {
+      if (c.threads > 0)
+        omp_set_num_threads(c.threads);
+      else
+        (void)configure_cpu_threads();
+#pragma omp parallel
+      { (void)omp_get_thread_num(); }
+    }
+    for (int k = 0; k < c.frames; ++k) {
+      fr.load(host + k * fb);
+      const double l0 = wall_seconds();
+      for (int done = 0; done < c.reps; ++done) fr.step();
+      r.loop_s += wall_seconds() - l0;  // the repetitions alone, as for one image
+      fr.copy_out(host + k * fb);
+    }
+  }
+  write_image(r.output, tall, host);
+  pc.mark("write");
+  r.e2e_s = wall_seconds() - t0;
+  if (c.check) {
+    // every frame against the CPU oracle of that frame alone
+    std::vector<uint8_t> in(static_cast<size_t>(tall.bytes())), ref(static_cast<size_t>(fb));
+    load_frames(in.data());
+    r.mismatches = 0;
+    for (int k = 0; k < c.frames; ++k) {
+      cpu_convolve(f, g, in.data() + k * fb, ref.data(), c.reps, CpuBackend::OpenMP, c.threads, c.border);
+      for (int64_t i = 0; i < fb; ++i) r.mismatches += ref[static_cast<size_t>(i)] != host[k * fb + i];
+    }
+  }
+  if (hip) r.since_exec_s = seconds_since_exec();
+  if (!hip) r.phases.clear();  // the CPU report carries no phase table (run_cpu)
   return r;
 }
 
@@ -1122,7 +1236,11 @@ std::string run_bench(const CliConfig& c) { return run_bench_impl(c); }
 
 AppReport run_app(const CliConfig& c, JobCache* cache) {
   AppReport r;
-  if (c.backend == Backend::Auto && cache == nullptr && c.checkpoint_every == 0 && c.converge_every == 0) {
+  if (c.frames > 1) {
+    PCONV_CHECK(cache == nullptr, "the resident service runs one image per job (--frames 1)");
+    r = run_frames(c);
+    r.gpus = c.backend == Backend::Hip ? 1 : 0;
+  } else if (c.backend == Backend::Auto && cache == nullptr && c.checkpoint_every == 0 && c.converge_every == 0) {
     r = run_auto(c);  // sets r.gpus (0 when the GPU was not used)
   } else if (c.backend == Backend::Cpu || c.backend == Backend::Omp) {
     r = run_cpu(c);
@@ -1136,7 +1254,8 @@ AppReport run_app(const CliConfig& c, JobCache* cache) {
     r = run_gpu1(c, cache);
     r.gpus = c.gpus;
   }
-  const double px = static_cast<double>(c.width) * static_cast<double>(c.height) * (r.reps_done >= 0 ? r.reps_done : c.reps);
+  const double px = static_cast<double>(c.width) * static_cast<double>(c.height) * c.frames *
+                    (r.reps_done >= 0 ? r.reps_done : c.reps);
   r.mpix_per_s = r.loop_s > 0 ? px / r.loop_s / 1e6 : 0.0;
   return r;
 }
@@ -1144,9 +1263,9 @@ AppReport run_app(const CliConfig& c, JobCache* cache) {
 std::string report_json(const CliConfig& c, const AppReport& r) {
   std::ostringstream os;
   const double px =
-      static_cast<double>(c.width) * static_cast<double>(c.height) * (r.reps_done >= 0 ? r.reps_done : c.reps);
+      static_cast<double>(c.width) * static_cast<double>(c.height) * c.frames * (r.reps_done >= 0 ? r.reps_done : c.reps);
   os << "{\"width\": " << c.width << ", \"height\": " << c.height << ", \"channels\": \""
-     << channels_name(c.channels) << "\", \"reps\": " << c.reps << ", \"filter\": \"" << c.filter
+     << channels_name(c.channels) << "\", \"frames\": " << c.frames << ", \"reps\": " << c.reps << ", \"filter\": \"" << c.filter
      << "\", \"border\": \"" << border_name(c.border) << "\", \"backend\": \""
      << (c.backend == Backend::Hip ? "hip" : c.backend == Backend::Omp ? "omp" : c.backend == Backend::Auto ? "auto" : "cpu")
      << "\", \"gpus\": " << r.gpus << ", \"kernel\": \"" << r.kernel << "\", \"halo\": " << r.halo

@@ -1,0 +1,158 @@
+// BatchEngine (see batch_engine.hpp).
+#include "pconv/batch_engine.hpp"
+
+#include <algorithm>
+#include <string>
+
+#include "pconv/schedule.hpp"
+#include "pconv/trace.hpp"
+
+namespace pconv {
+
+BatchEngine::BatchEngine(const ImageGeom& geom, const Filter& filter, int capacity, const EngineOptions& opt)
+    : geom_(geom), filter_(filter), opt_(opt), capacity_(capacity) {
+  geom_.validate();
+  PCONV_CHECK(capacity >= 1, "BatchEngine: capacity must be >= 1");
+  // A batch runs on the temporal kernels only (launch_stencil routes Auto to
+  // them for every step count); say so here, not at the first launch.
+  const KernelVariant v = opt.variant;
+  PCONV_CHECK(v == KernelVariant::Auto || v == KernelVariant::Temporal || v == KernelVariant::FloatTemporal,
+              "BatchEngine: batch not supported by kernel '" + std::string(kernel_variant_name(v)) + "'");
+  PlanConfig c;
+  c.fuse = opt.fuse;
+  c = normalize_plan_config(c, 0, kMaxFusedSteps);
+  opt_.fuse = c.fuse;
+  opt_.halo_depth = c.fuse;
+  set_device(opt_.device);
+  lay_ = FrameLayout::make(geom_.row_bytes(), geom_.height, opt_.fuse);
+  stride_ = lay_.bytes();  // total_rows x pitch: whole pitches, a multiple of 16
+  if (opt_.compute_stream) {
+    cs_ = opt_.compute_stream;
+  } else {
+    own_cs_ = Stream::create(0);
+    cs_ = own_cs_.get();
+  }
+  // Both allocations are zeroed once: pad columns, ghost rows and the frames
+  // of images a partial batch leaves out are never written afterwards.
+  for (auto& f : frame_) {
+    f = DeviceBuffer(static_cast<size_t>(stride_ * capacity_));
+    if (opt_.kernel_copies)
+      launch_fill_zero(f.data(), static_cast<int64_t>(f.size()), cs_);
+    else
+      PCONV_HIP_CHECK(hipMemsetAsync(f.data(), 0, f.size(), cs_));
+  }
+  ev_sync_ = Event::create();
+  ev_t0_ = Event::create(true);
+  ev_t1_ = Event::create(true);
+  PCONV_HIP_CHECK(hipStreamSynchronize(cs_));
+}
+
+BatchEngine::~BatchEngine() {
+  if (cs_) (void)hipStreamSynchronize(cs_);
+}
+
+void BatchEngine::check_n(const char* who, int n) const {
+  PCONV_CHECK(n >= 0 && n <= capacity_, std::string(who) + ": " + std::to_string(n) + " images outside [0, capacity " +
+                                            std::to_string(capacity_) + "]");
+}
+
+// Copies: n pitched 2-D copies, one per image — the call every other engine of
+// this library uses for its rows.  One hipMemcpy3DAsync could describe the
+// whole batch (the frames sit a whole number of pitches apart), but it has not
+// been timed against this form; tools/batch_sweep.py reports the end-to-end
+// time these copies give.
+void BatchEngine::upload(const uint8_t* p, int n, bool device) {
+  check_n("BatchEngine::upload", n);
+  PCONV_CHECK(p != nullptr || n == 0, "BatchEngine::upload: null source");
+  const int64_t rb = lay_.row_bytes, img = geom_.bytes();
+  for (int b = 0; b < n; ++b) {
+    uint8_t* d = frame_at(cur_) + b * stride_;
+    if (opt_.kernel_copies)
+      launch_copy_rows(p + b * img, rb, d, lay_.pitch, rb, lay_.rows, cs_);
+    else
+      PCONV_HIP_CHECK(hipMemcpy2DAsync(d, lay_.pitch, p + b * img, rb, rb, lay_.rows,
+                                       device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, cs_));
+  }
+}
+
+void BatchEngine::download(uint8_t* p, int n, bool device) {
+  check_n("BatchEngine::download", n);
+  PCONV_CHECK(p != nullptr || n == 0, "BatchEngine::download: null destination");
+  const int64_t rb = lay_.row_bytes, img = geom_.bytes();
+  for (int b = 0; b < n; ++b) {
+    const uint8_t* s = frame_at(cur_) + b * stride_;  // cur_ follows the launches: the newest frames
+    if (opt_.kernel_copies)
+      launch_copy_rows(s, lay_.pitch, p + b * img, rb, rb, lay_.rows, cs_);
+    else
+      PCONV_HIP_CHECK(hipMemcpy2DAsync(p + b * img, rb, s, lay_.pitch, rb, lay_.rows,
+                                       device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, cs_));
+  }
+}
+
+void BatchEngine::run(int reps, int n) {
+  TraceRange tr("pconv.batch.run");
+  PCONV_CHECK(reps >= 0, "repetitions must be >= 0");
+  check_n("BatchEngine::run", n);
+  Band band;
+  band.rows = geom_.height;
+  PlanConfig c;
+  c.fuse = supports_fusion(filter_, opt_.variant) ? opt_.fuse : 1;
+  c.halo_depth = opt_.fuse;
+  const std::vector<Phase> ph = plan_band(band, reps, c);
+  stats_ = RunStats{};
+  wall_t0_ = wall_seconds();
+  if (opt_.timing) ev_t0_.record(cs_);
+  if (n > 0) {
+    // First use of a (geometry, steps, batch) tunes inside launch_stencil on
+    // this very launch, frame[cur] -> frame[cur ^ 1] (BandEngine's rule: the
+    // input is only read, every candidate writes the same bytes), and never on
+    // a capturing stream.
+    for (const auto& p : ph) {
+      for (const auto& l : p.launches) {
+        StencilLaunch a;
+        a.src = frame_at(cur_);
+        a.dst = frame_at(cur_ ^ 1);
+        a.pitch = lay_.pitch;
+        a.row_bytes = lay_.row_bytes;
+        a.r0 = l.lo;
+        a.r1 = l.hi;
+        a.frame_lo = -lay_.halo;
+        a.frame_hi = lay_.rows + lay_.halo;
+        a.steps = l.steps;
+        a.g_row0 = 0;
+        a.height = geom_.height;
+        a.border = opt_.border;
+        a.batch = n;
+        a.batch_stride = stride_;
+        launch_stencil(filter_, geom_.channels, a, cs_, opt_.variant);
+        ++stats_.launches;
+      }
+      cur_ ^= 1;
+    }
+  }
+  if (opt_.timing) {
+    ev_t1_.record(cs_);
+    timing_pending_ = true;
+  }
+}
+
+void BatchEngine::wait_stream(hipStream_t s) {
+  ev_sync_.record(s);
+  ev_sync_.wait_on(cs_);
+}
+
+void BatchEngine::signal_stream(hipStream_t s) {
+  ev_sync_.record(cs_);
+  ev_sync_.wait_on(s);
+}
+
+void BatchEngine::synchronize() {
+  PCONV_HIP_CHECK(hipStreamSynchronize(cs_));
+  if (timing_pending_) {
+    stats_.loop_ms = Event::elapsed_ms(ev_t0_, ev_t1_);
+    stats_.wall_ms = (wall_seconds() - wall_t0_) * 1e3;
+    timing_pending_ = false;
+  }
+}
+
+}  // namespace pconv

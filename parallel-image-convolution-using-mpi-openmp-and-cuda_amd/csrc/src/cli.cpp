@@ -47,6 +47,11 @@ std::string help_text(const std::string& prog) {
          "  --kernel {auto,binomial,temporal,int9,float9,float_temporal}\n"
          "  --out PATH                output file (default: blur_<image> next to the input)\n"
          "  --synthetic SEED          use a deterministic random image instead of reading the file\n"
+         "  --frames N                the file holds N images of width x height back to back (default 1); each\n"
+         "                            is convolved on its own and the output has the same layout.  hip: all\n"
+         "                            frames advance in the same fused launches on 1 GPU; --synthetic makes\n"
+         "                            frame k from SEED + k.  Not with --gpus > 1, --server, --bench,\n"
+         "                            --backend auto, --checkpoint-every, --converge-every, --graph\n"
          "  --check                   verify the result against the CPU oracle\n"
          "  --json                    print a JSON metrics line\n"
          "  --threads N               OpenMP threads for --backend omp\n"
@@ -147,6 +152,8 @@ CliConfig parse_cli(const std::vector<std::string>& args) {
     } else if (a == "--synthetic") {
       c.synthetic = true;
       c.seed = static_cast<uint64_t>(parse_int(next("--synthetic"), "--synthetic", 0, INT64_MAX));
+    } else if (a == "--frames") {
+      c.frames = static_cast<int>(parse_int(next("--frames"), "--frames", 1, 1 << 20));
     } else if (a == "--check") {
       c.check = true;
     } else if (a == "--json") {
@@ -233,6 +240,18 @@ CliConfig parse_cli(const std::vector<std::string>& args) {
     PCONV_FAIL("--converge-every cannot be combined with --checkpoint-every");
   if (c.converge_every > 0 && c.bench_steps > 0) PCONV_FAIL("--converge-every cannot be combined with --bench");
   if (c.backend == Backend::Auto && c.bench_steps > 0) PCONV_FAIL("--bench runs on the GPU (--backend hip)");
+  if (c.frames > 1) {
+    const auto refuse = [](const char* what) {
+      PCONV_FAIL(std::string("--frames above 1 cannot be combined with ") + what);
+    };
+    if (c.gpus > 1) refuse("--gpus above 1 (a batch runs on one GPU)");
+    if (!c.server.empty()) refuse("--server");
+    if (c.bench_steps > 0) refuse("--bench");
+    if (c.backend == Backend::Auto) refuse("--backend auto");
+    if (c.checkpoint_every > 0) refuse("--checkpoint-every");
+    if (c.converge_every > 0) refuse("--converge-every");
+    if (c.graph) refuse("--graph (a batch is not captured into a hipGraph)");
+  }
   if (c.emulate_world > 0 && (c.bench_steps == 0 || c.gpus != 1))
     PCONV_FAIL("--emulate needs --bench and --gpus 1 (one process times one rank of the split)");
   return c;

@@ -10,6 +10,7 @@
 #include <cstring>
 
 #include "pconv/app.hpp"
+#include "pconv/batch_engine.hpp"
 #include "pconv/cpu_stencil.hpp"
 #include "pconv/device.hpp"
 #include "pconv/engine.hpp"
@@ -408,9 +409,11 @@ PYBIND11_MODULE(_pconv_native, m) {
       "launch_stencil",
       [](py::object filter, const std::string& ch, uintptr_t src, uintptr_t dst, int64_t pitch, int64_t row_bytes,
          int64_t r0, int64_t r1, int64_t frame_lo, int64_t frame_hi, int steps, int64_t g_row0, int64_t height,
-         uintptr_t stream, const std::string& variant, const std::string& border) {
+         uintptr_t stream, const std::string& variant, const std::string& border, int batch, int64_t batch_stride) {
         StencilLaunch a;
         a.border = parse_border(border);
+        a.batch = batch;
+        a.batch_stride = batch_stride;
         a.src = reinterpret_cast<const uint8_t*>(src);
         a.dst = reinterpret_cast<uint8_t*>(dst);
         a.pitch = pitch;
@@ -428,7 +431,7 @@ PYBIND11_MODULE(_pconv_native, m) {
       py::arg("filter"), py::arg("channels"), py::arg("src"), py::arg("dst"), py::arg("pitch"), py::arg("row_bytes"),
       py::arg("r0"), py::arg("r1"), py::arg("frame_lo"), py::arg("frame_hi"), py::arg("steps") = 1,
       py::arg("g_row0") = 0, py::arg("height") = (int64_t(1) << 40), py::arg("stream") = 0,
-      py::arg("variant") = "auto", py::arg("border") = "zero");
+      py::arg("variant") = "auto", py::arg("border") = "zero", py::arg("batch") = 1, py::arg("batch_stride") = 0);
   m.def(
       "launch_residual",
       [](py::object filter, const std::string& ch, uintptr_t src, int64_t pitch, int64_t row_bytes, int64_t r0,
@@ -472,12 +475,13 @@ PYBIND11_MODULE(_pconv_native, m) {
   });
   m.def(
       "swar_model",
-      [](int steps, const std::string& ch, int64_t rows, int64_t row_bytes) {
-        const SwarShape s = pick_swar_shape(steps, channel_count(parse_channels(ch)), rows, row_bytes);
+      [](int steps, const std::string& ch, int64_t rows, int64_t row_bytes, int batch) {
+        PCONV_CHECK(batch >= 1, "swar_model: batch must be >= 1");
+        const SwarShape s = pick_swar_shape(steps, channel_count(parse_channels(ch)), rows, row_bytes, batch);
         return py::make_tuple(py::make_tuple(s.lw, s.m, s.nw),
-                              swar_launch_cycles(s, steps, channel_count(parse_channels(ch)), rows, row_bytes));
+                              swar_launch_cycles(s, steps, channel_count(parse_channels(ch)), rows, row_bytes, batch));
       },
-      py::arg("steps"), py::arg("channels"), py::arg("rows"), py::arg("row_bytes"));
+      py::arg("steps"), py::arg("channels"), py::arg("rows"), py::arg("row_bytes"), py::arg("batch") = 1);
   m.def("set_autotune", &set_shape_tuning, py::arg("on"),
         "Time the model's best tile shapes on first use of a launch geometry (default on); returns the previous "
         "setting.");
@@ -511,18 +515,19 @@ PYBIND11_MODULE(_pconv_native, m) {
         "XCD-aware (bijective, per-XCD contiguous) tile order of the SWAR kernel.");
   m.def(
       "swar_model_table",
-      [](int steps, const std::string& ch, int64_t rows, int64_t row_bytes) {
+      [](int steps, const std::string& ch, int64_t rows, int64_t row_bytes, int batch) {
         // every shape: (lw, m, nw, vgpr, lds, measured, predicted cycles)
+        PCONV_CHECK(batch >= 1, "swar_model_table: batch must be >= 1");
         const int c = channel_count(parse_channels(ch));
         py::list out;
         for (const auto& s : swar_shapes()) {
           const SwarResources r = swar_resources(s, c);
           out.append(py::make_tuple(s.lw, s.m, s.nw, r.vgpr, r.lds, r.measured,
-                                    swar_launch_cycles(s, steps, c, rows, row_bytes)));
+                                    swar_launch_cycles(s, steps, c, rows, row_bytes, batch)));
         }
         return out;
       },
-      py::arg("steps"), py::arg("channels"), py::arg("rows"), py::arg("row_bytes"));
+      py::arg("steps"), py::arg("channels"), py::arg("rows"), py::arg("row_bytes"), py::arg("batch") = 1);
   m.def("auto_fuse",
         [](py::object filter, const std::string& v, int64_t frame_bytes, int channels) {
           return auto_fuse(make_filter(filter), parse_variant(v), frame_bytes, channels);
@@ -733,6 +738,62 @@ PYBIND11_MODULE(_pconv_native, m) {
            py::keep_alive<1, 2>())
       .def("attach_null_transport",
            [](BandEngine& e) { e.set_transport(std::make_shared<NullTransport>()); });
+
+  // Up to `capacity` whole images of one geometry, one fused launch per
+  // `fuse` repetitions for all of them (batch_engine.hpp).
+  py::class_<BatchEngine>(m, "BatchEngine")
+      .def(py::init([](int64_t w, int64_t h, const std::string& ch, int capacity, py::object filter, int device,
+                       int fuse, const std::string& variant, const std::string& border) {
+             EngineOptions o;
+             o.border = parse_border(border);
+             o.device = device;
+             o.fuse = fuse;
+             o.variant = parse_variant(variant);
+             return std::make_unique<BatchEngine>(make_geom(w, h, ch), make_filter(filter), capacity, o);
+           }),
+           py::arg("width"), py::arg("height"), py::arg("channels"), py::arg("capacity"),
+           py::arg("filter") = "gaussian", py::arg("device") = 0, py::arg("fuse") = 1, py::arg("variant") = "auto",
+           py::arg("border") = "zero")
+      .def_property_readonly("capacity", &BatchEngine::capacity)
+      .def_property_readonly("border", [](const BatchEngine& e) { return std::string(border_name(e.options().border)); })
+      .def_property_readonly("fuse", [](const BatchEngine& e) { return e.options().fuse; })
+      .def_property_readonly("halo", [](const BatchEngine& e) { return e.layout().halo; })
+      .def_property_readonly("pitch", [](const BatchEngine& e) { return e.layout().pitch; })
+      .def_property_readonly("row_bytes", [](const BatchEngine& e) { return e.layout().row_bytes; })
+      .def_property_readonly("batch_stride", &BatchEngine::batch_stride)
+      .def_property_readonly("compute_stream",
+                             [](const BatchEngine& e) { return reinterpret_cast<uintptr_t>(e.compute_stream()); })
+      .def(
+          "upload",
+          [](BatchEngine& e, py::buffer host, int n) {
+            const HostView v = host_view(host, false);
+            PCONV_CHECK(n >= 0 && v.size >= n * e.geom().bytes(), "host buffer too small");
+            e.upload(v.ptr, n);
+          },
+          py::arg("host"), py::arg("n"))
+      .def(
+          "upload_ptr",
+          [](BatchEngine& e, uintptr_t ptr, int n, bool device) {
+            e.upload(reinterpret_cast<const uint8_t*>(ptr), n, device);
+          },
+          py::arg("ptr"), py::arg("n"), py::arg("device") = false)
+      .def(
+          "download",
+          [](BatchEngine& e, py::buffer host, int n) {
+            const HostView v = host_view(host, true);
+            PCONV_CHECK(n >= 0 && v.size >= n * e.geom().bytes(), "host buffer too small");
+            e.download(v.ptr, n);
+          },
+          py::arg("host"), py::arg("n"))
+      .def(
+          "download_ptr",
+          [](BatchEngine& e, uintptr_t ptr, int n, bool device) { e.download(reinterpret_cast<uint8_t*>(ptr), n, device); },
+          py::arg("ptr"), py::arg("n"), py::arg("device") = false)
+      .def("wait_stream", [](BatchEngine& e, uintptr_t s) { e.wait_stream(reinterpret_cast<hipStream_t>(s)); })
+      .def("signal_stream", [](BatchEngine& e, uintptr_t s) { e.signal_stream(reinterpret_cast<hipStream_t>(s)); })
+      .def("run", &BatchEngine::run, py::arg("reps"), py::arg("n"), py::call_guard<py::gil_scoped_release>())
+      .def("synchronize", &BatchEngine::synchronize, py::call_guard<py::gil_scoped_release>())
+      .def_property_readonly("stats", &BatchEngine::last_stats);
 
   py::class_<BandPipeline>(m, "BandPipeline")
       .def(py::init([](int64_t w, int64_t h, const std::string& ch, py::object filter, int rank, int world,

@@ -322,6 +322,204 @@ def convolve_until_stable(image, max_reps: int, filter="gaussian", check_every: 
     return (torch.from_numpy(out).to(image.device) if is_tensor else out), info
 
 
+# ---- image batches ----------------------------------------------------------
+
+
+class BatchEngine:
+    """Persistent single-GPU engine for up to ``capacity`` images of ONE
+    geometry: all of a call's images advance in the same fused launches
+    (``ceil(reps / fuse)`` launches whatever their number), so small images
+    fill the chip together instead of paying a launch's latency each.
+
+    ``run_numpy`` / ``run_tensor`` / ``__call__`` take a stack of
+    ``n <= capacity`` images, ``(n, H, W)`` or ``(n, H, W, C)``, and return the
+    same container type; a CUDA tensor never leaves the device.
+    """
+
+    def __init__(self, width: int, height: int, channels: str = "grey", capacity: int = 1, filter="gaussian",
+                 device: int = 0, fuse: Optional[int] = None, variant: str = "auto", border: str = "zero"):
+        n = require_native()
+        self.border = check_border(border)
+        self.filter = get_filter(filter)
+        nf = self.filter.to_native()
+        if fuse is None:
+            ch = {"grey": 1, "rgb": 3, "rgba": 4}[channels]
+            fuse = n.auto_fuse(nf, variant, int(width) * int(height) * ch, ch)
+        self.width, self.height, self.channels = int(width), int(height), channels
+        self.device = int(device)
+        self._eng = n.BatchEngine(self.width, self.height, channels, int(capacity), nf, self.device, fuse=int(fuse),
+                                  variant=variant, border=self.border)
+        self.capacity = self._eng.capacity
+        self.row_bytes = self._eng.row_bytes
+
+    @property
+    def fuse(self) -> int:
+        return self._eng.fuse
+
+    @property
+    def stats(self):
+        return self._eng.stats
+
+    def _check_stack(self, shape) -> int:
+        shape = tuple(int(s) for s in shape)
+        if len(shape) not in (3, 4) or image_geometry(shape[1:]) != (self.width, self.height, self.channels):
+            raise ValueError(f"stack of shape {shape} does not hold {self.width}x{self.height} {self.channels} images")
+        if shape[0] > self.capacity:
+            raise ValueError(f"{shape[0]} images exceed the engine's capacity {self.capacity}")
+        return shape[0]
+
+    def run_numpy(self, stack: np.ndarray, reps: int) -> np.ndarray:
+        src = np.ascontiguousarray(stack, dtype=np.uint8)
+        n = self._check_stack(src.shape)
+        out = np.empty_like(src)
+        if n == 0:
+            return out
+        self._eng.upload(src.reshape(-1), n)
+        self._eng.run(int(reps), n)
+        self._eng.download(out.reshape(-1), n)
+        self._eng.synchronize()
+        return out
+
+    def run_tensor(self, stack: torch.Tensor, reps: int) -> torch.Tensor:
+        if stack.device.type != "cuda":
+            return torch.from_numpy(self.run_numpy(stack.numpy(), reps))
+        src = stack.contiguous()
+        n = self._check_stack(src.shape)
+        out = torch.empty_like(src)
+        if n == 0:
+            return out
+        ts = torch.cuda.current_stream(src.device).cuda_stream
+        self._eng.wait_stream(ts)
+        self._eng.upload_ptr(src.data_ptr(), n, device=True)
+        self._eng.run(int(reps), n)
+        self._eng.download_ptr(out.data_ptr(), n, device=True)
+        self._eng.signal_stream(ts)
+        src.record_stream(torch.cuda.current_stream(src.device))
+        return out
+
+    def __call__(self, stack, reps: int):
+        if isinstance(stack, torch.Tensor):
+            return self.run_tensor(stack, reps)
+        return self.run_numpy(np.asarray(stack), reps)
+
+
+# convolve_batch's own engine cache (the single-image engines keep theirs).
+_BATCH_ENGINES: "OrderedDict[tuple, BatchEngine]" = OrderedDict()
+_MAX_CACHED_BATCH = 2
+# Memory policy of batch_size=None, not a tuned number: the two ping-pong
+# allocations of a BatchEngine together stay within this many bytes.
+_BATCH_BYTES = 1 << 30
+
+
+def _cached_batch_engine(w, h, ch, capacity, flt, device, fuse, variant, border) -> BatchEngine:
+    key = (w, h, ch, capacity, flt.taps, flt.divisor, device, fuse, variant, border)
+    eng = _BATCH_ENGINES.get(key)
+    if eng is None:
+        # make room first: two engines of the memory bound are the cache's most
+        while len(_BATCH_ENGINES) >= _MAX_CACHED_BATCH:
+            _BATCH_ENGINES.popitem(last=False)
+        eng = BatchEngine(w, h, ch, capacity, flt, device=device, fuse=fuse, variant=variant, border=border)
+        _BATCH_ENGINES[key] = eng
+    else:
+        _BATCH_ENGINES.move_to_end(key)
+    return eng
+
+
+def _frame_bytes(w: int, h: int, ch: str, fuse: int) -> int:
+    """Bytes of one device frame (csrc/include/pconv/image.hpp, FrameLayout):
+    16 pad bytes, the row, at least 32 more, rounded to 128; ``fuse`` ghost
+    rows above and below."""
+    row_bytes = w * {"grey": 1, "rgb": 3, "rgba": 4}[ch]
+    pitch = -(-(16 + row_bytes + 32) // 128) * 128
+    return pitch * (h + 2 * fuse)
+
+
+def _as_stack(images):
+    """``images`` as one uint8 stack ``(N, H, W[, C])``; (stack, is_tensor)."""
+    if isinstance(images, torch.Tensor):
+        if images.dtype != torch.uint8:
+            raise TypeError("image tensor must be uint8")
+        return images, True
+    if isinstance(images, np.ndarray):
+        if images.dtype != np.uint8:
+            raise TypeError("image array must be uint8")
+        return images, False
+    seq = list(images)
+    if not seq:
+        raise ValueError("an empty sequence of images has no geometry: pass an array or tensor of shape (0, H, W[, C])")
+    shapes = {tuple(im.shape) for im in seq}
+    if len(shapes) != 1:
+        raise ValueError(f"images of a batch must have one shape, got {sorted(shapes)}")
+    if all(isinstance(im, torch.Tensor) for im in seq):
+        if any(im.dtype != torch.uint8 for im in seq):
+            raise TypeError("image tensor must be uint8")
+        return torch.stack(seq), True
+    arrs = [im.cpu().numpy() if isinstance(im, torch.Tensor) else np.asarray(im) for im in seq]
+    if any(a.dtype != np.uint8 for a in arrs):
+        raise TypeError("image array must be uint8")
+    return np.stack(arrs), False
+
+
+def convolve_batch(images, reps: int = 1, filter="gaussian", backend: str = "auto", device: Optional[int] = None,
+                   fuse: Optional[int] = None, variant: str = "auto", threads: int = 0, border: str = "zero",
+                   batch_size: Optional[int] = None):
+    """``convolve`` for N same-size 8-bit images at once.
+
+    ``images``: an ``(N, H, W)`` array or tensor (grey), an ``(N, H, W, C)``
+    one with ``C`` in {1, 3, 4}, or a sequence of N same-shape images (stacked).
+    The result equals ``np.stack([convolve(img, reps, ...) for img in images])``
+    on every backend, in the input's container type and on its device (a
+    sequence returns a stack).
+
+    On the ``hip`` backend the images advance together through one cached
+    :class:`BatchEngine`, ``batch_size`` at a time (the last chunk shorter).
+    ``batch_size=None``: the largest n <= N whose two device allocations stay
+    within 1 GiB (at least 1) — a memory policy, not a tuned number.  The
+    other backends loop over the images.
+    """
+    if reps < 0:
+        raise ValueError("reps must be >= 0")
+    if batch_size is not None and int(batch_size) < 1:
+        raise ValueError("batch_size must be >= 1")
+    flt = get_filter(filter)
+    check_border(border)
+    stack, is_tensor = _as_stack(images)
+    shape = tuple(int(s) for s in stack.shape)
+    if len(shape) not in (3, 4):
+        raise ValueError(f"unsupported batch shape {shape}: expected (N, H, W) or (N, H, W, 1|3|4)")
+    w, h, ch = image_geometry(shape[1:])
+    n_img = shape[0]
+    is_cuda = is_tensor and stack.is_cuda
+    if backend == "auto":
+        backend = "hip" if is_cuda else _default_backend()
+    if backend not in ("hip", "omp", "cpu", "numpy"):
+        raise ValueError(f"unknown backend {backend!r} (hip|omp|cpu|numpy|auto)")
+    if n_img == 0:
+        return torch.empty_like(stack) if is_tensor else np.empty(shape, dtype=np.uint8)
+
+    if backend != "hip":
+        outs = [convolve(stack[i], reps, flt, backend=backend, threads=threads, border=border) for i in range(n_img)]
+        return torch.stack(outs) if is_tensor else np.stack(outs)
+
+    n = require_native()
+    if device is None:
+        device = stack.device.index if is_cuda else 0
+    device = int(device or 0)
+    if fuse is None:
+        c = {"grey": 1, "rgb": 3, "rgba": 4}[ch]
+        fuse = n.auto_fuse(flt.to_native(), variant, w * h * c, c)
+    fuse = int(fuse)
+    if batch_size is None:
+        cap = max(1, min(n_img, _BATCH_BYTES // (2 * _frame_bytes(w, h, ch, fuse))))
+    else:
+        cap = min(n_img, int(batch_size))
+    eng = _cached_batch_engine(w, h, ch, cap, flt, device, fuse, variant, border)
+    if n_img <= cap:
+        return eng(stack, reps)
+    outs = [eng(stack[i:i + cap], reps) for i in range(0, n_img, cap)]
+    return torch.cat(outs) if is_tensor else np.concatenate(outs)
+
+
 def convolve_file(path: str, width: int, height: int, reps: int, channels: str = "grey", filter="gaussian",
                   out: Optional[str] = None, backend: str = "auto", device: Optional[int] = None,
                   border: str = "zero") -> str:
