@@ -28,7 +28,7 @@ __version__ = "0.1.0"
 from ._native import native, native_available  # noqa: E402  (loads torch first)
 from .models.filters import Filter, get_filter, list_filters  # noqa: E402
 from .ops.stencil import convolve, convolve_file, convolve_until_stable, residual, Engine, StableInfo  # noqa: E402
-from .ops.stencil import BatchEngine, convolve_batch  # noqa: E402
+from .ops.stencil import BatchEngine, convolve_batch, convolve_batch_until_stable, residual_batch  # noqa: E402
 from .models.pipeline import FilterPipeline  # noqa: E402
 from .ops.reference import numpy_convolve, numpy_residual  # noqa: E402
 from .utils.raw_io import read_raw, write_raw, output_path_for, synthetic_image  # noqa: E402
@@ -44,6 +44,8 @@ __all__ = [
     "Engine",
     "BatchEngine",
     "convolve_batch",
+    "convolve_batch_until_stable",
+    "residual_batch",
     "FilterPipeline",
     "numpy_convolve",
     "residual",

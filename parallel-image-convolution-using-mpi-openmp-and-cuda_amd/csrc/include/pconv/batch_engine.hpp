@@ -7,12 +7,24 @@
 // a batch widens the grid instead of lengthening the queue of launches.
 //
 // No bands, neighbours or transport: each image is the band {y0 = 0, rows = H}
-// of BandEngine, and the plan is plan_band's for that band.  Out of scope here
-// (see docs/ARCHITECTURE.md §5): hipGraph capture, residual / run-until-stable,
-// images of different sizes, more than one GPU.
+// of BandEngine, and the plan is plan_band's for that band.
+//
+// Fixed points: residual(n) counts, per image and in ONE launch of the
+// residual kernel, the bytes one more repetition would change;
+// run_until_stable advances all n images in chunks with such a check after
+// each and reports for every image what a single-image run of it would have
+// reported.  Converged images keep advancing with the rest (they rewrite the
+// same bytes) until the last image converges or max_reps is reached.
+//
+// Out of scope here (see docs/ARCHITECTURE.md §5): hipGraph capture, retiring
+// converged images from the launches (compaction), images of different sizes,
+// more than one GPU.
 #pragma once
 
 #include <hip/hip_runtime_api.h>
+
+#include <cstdint>
+#include <vector>
 
 #include "pconv/device.hpp"
 #include "pconv/engine.hpp"
@@ -50,6 +62,24 @@ class BatchEngine {
   // Enqueue `reps` repetitions of images [0, n) (async).
   void run(int reps, int n);
 
+  // Per-image counts of the bytes one more repetition would change in the
+  // newest frames of images [0, n): one residual launch.  Synchronises.
+  std::vector<uint64_t> residual(int n);
+  // Chunks of `check_every` repetitions of images [0, n) (the last one
+  // shorter), a per-image residual check after each; ends when every image has
+  // converged or at max_reps.  Entry b is what BandEngine::run_until_stable
+  // returns for image b alone: an image whose count is zero for the first time
+  // at check j is converged there (reps_done = the repetitions made by then,
+  // checks = j, residual 0) and final — a later non-zero count for it is an
+  // error; the others end with reps_done = max_reps, every check made and
+  // their last count.  The frames hold max(reps made) repetitions, which for a
+  // converged image are its fixed point's bytes.  last_stats() afterwards
+  // carries the summed launches and the host-timed loop.
+  std::vector<StableStats> run_until_stable(int max_reps, int check_every, int n);
+  // Diagnostics: ms of each of `launches` residual launches over images [0, n)
+  // of the current frames (stream events around the launch alone).
+  std::vector<double> time_residual(int launches, int n);
+
   void wait_stream(hipStream_t s);
   void signal_stream(hipStream_t s);
   void synchronize();
@@ -57,6 +87,9 @@ class BatchEngine {
 
  private:
   void check_n(const char* who, int n) const;
+  void launch_batch_residual(int n);
+  void enqueue_residual(int n);
+  std::vector<uint64_t> finish_residual(int n);
 
   ImageGeom geom_;
   Filter filter_;
@@ -66,6 +99,10 @@ class BatchEngine {
   int64_t stride_ = 0;
   DeviceBuffer frame_[2];
   int cur_ = 0;
+  DeviceBuffer res_count_;          // residual(): `capacity` 64-bit device counters (allocated on first use)
+  PinnedBuffer res_host_;           // pinned words the running counts are read back into
+  Event res_ev_;                    // the latest read-back has landed
+  std::vector<uint64_t> res_seen_;  // the running counts at the latest check read
   Stream own_cs_;
   hipStream_t cs_ = nullptr;
   Event ev_t0_, ev_t1_, ev_sync_;

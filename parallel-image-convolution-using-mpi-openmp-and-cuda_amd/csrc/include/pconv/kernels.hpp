@@ -44,7 +44,7 @@ struct StencilLaunch {
   // kernels only (they apply it at every fused step): Auto routes every step
   // count to them, the single-step variants reject it.
   Border border = Border::Zero;
-  // Image batch (temporal kernels only): `batch` independent images of this
+  // Image batch (temporal kernels and the residual kernel): `batch` independent images of this
   // geometry advance in the one launch.  Every other field describes ONE image
   // and applies to each; image b's frame lies b * batch_stride bytes after
   // image 0's, in src and dst alike (ignored when batch == 1).  Images never
@@ -88,9 +88,15 @@ void prepare_float_temporal(const Filter& f, Channels ch, const StencilLaunch& a
 // [a.r0, a.r1) and the bytes of [0, row_bytes) with step(x) != x are counted.
 // Nothing is stored but the count, ADDED to *counter (device memory, zeroed by
 // the caller): zero means the rows are a fixed point of the repetition.  Reads
-// src, pitch, row_bytes, r0, r1, frame_lo, frame_hi, g_row0, height and border
-// (dst and steps are ignored); the rows are clipped to the global image and
-// validated against the frame like a one-step launch_stencil.
+// src, pitch, row_bytes, r0, r1, frame_lo, frame_hi, g_row0, height, border,
+// batch and batch_stride (dst and steps are ignored); the rows are clipped to
+// the global image and validated against the frame like a one-step
+// launch_stencil.
+// Image batch: `counter` points at a.batch consecutive 64-bit counters and
+// image b's count (its frame b * batch_stride bytes after image 0's) is ADDED
+// to counter[b], all in the one launch; no counter beyond a.batch is touched.
+// The batch guards are launch_stencil's (check_batch), every geometry guard
+// holds per image, and batch x workgroups per image must stay below 2^31.
 void launch_residual(const Filter& f, Channels ch, const StencilLaunch& a, uint64_t* counter, hipStream_t stream);
 // Rows one workgroup of the residual kernel covers (tests place image heights around it).
 constexpr int kResidualBlockRows = 32;

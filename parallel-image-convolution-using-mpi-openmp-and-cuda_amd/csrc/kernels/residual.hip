@@ -13,6 +13,14 @@
 // workgroup's four waves through LDS, and one 64-bit atomic add per workgroup
 // (none when its count is zero) lands on the device counter.
 //
+// An image batch (StencilLaunch::batch) is a run-time argument, as in the
+// temporal kernels: the flat grid is batch x blocks_per_image workgroups,
+// image-major, so a workgroup never spans two images.  Its image comes from
+// the workgroup id (scalar) and does two things only: it moves the frame
+// pointer by img * batch_stride (64-bit) before anything else, and it picks
+// the counter the workgroup's atomic add lands on, counter[img].  One image is
+// the same instantiations on the same grid, adding to counter[0].
+//
 // Borders are applied to the registers, not read from the frame: rows outside
 // the global image are zeros (Zero) or the image's first / last row
 // (Replicate); the bytes left of column 0 and right of the row's last byte
@@ -91,14 +99,21 @@ __device__ __forceinline__ u32 changed(const Row24& a, const Row24& b, const Row
 }
 
 // Workgroup = 64 lanes along the row x 4 waves down the rows; workgroups in a
-// flat grid, the row's chunks fastest.
+// flat grid, the row's chunks fastest, then the image's block rows, then the
+// images of the batch.
 template <int CH, bool FLOAT, bool REP>
 __global__ __launch_bounds__(256) void k_residual(const uint8_t* __restrict__ src, int64_t pitch, int row_bytes,
                                                   int r0, int r1, Taps9 tp, int img_lo, int img_hi, int blocks_x,
+                                                  int blocks_per_image, int64_t batch_stride,
                                                   unsigned long long* __restrict__ counter) {
   __shared__ u32 part[4];
-  const int bx = static_cast<int>(blockIdx.x % static_cast<unsigned>(blocks_x));
-  const int by = static_cast<int>(blockIdx.x / static_cast<unsigned>(blocks_x));
+  // Image of the batch: from the workgroup id (scalar); it only moves the
+  // frame pointer and picks the counter.
+  const unsigned img = blockIdx.x / static_cast<unsigned>(blocks_per_image);
+  const unsigned blk = blockIdx.x - img * static_cast<unsigned>(blocks_per_image);
+  src += static_cast<int64_t>(img) * batch_stride;
+  const int bx = static_cast<int>(blk % static_cast<unsigned>(blocks_x));
+  const int by = static_cast<int>(blk / static_cast<unsigned>(blocks_x));
   const int x = (bx * 64 + static_cast<int>(threadIdx.x)) * 16;
   const int rs = r0 + (by * 4 + static_cast<int>(threadIdx.y)) * kRpt;
   u32 cnt = 0;
@@ -122,7 +137,7 @@ __global__ __launch_bounds__(256) void k_residual(const uint8_t* __restrict__ sr
   __syncthreads();
   if (threadIdx.x == 0 && threadIdx.y == 0) {
     const u32 total = part[0] + part[1] + part[2] + part[3];
-    if (total != 0) atomicAdd(counter, static_cast<unsigned long long>(total));
+    if (total != 0) atomicAdd(counter + img, static_cast<unsigned long long>(total));
   }
 }
 
@@ -138,16 +153,18 @@ void launch_ch(const Filter& f, const StencilLaunch& a, uint64_t* counter, hipSt
   const auto [lo, hi] = image_rows_in_frame(a);
   const int64_t bx = ceil_div<int64_t>(ceil_div<int64_t>(a.row_bytes, 16), 64);
   const int64_t by = ceil_div<int64_t>(rows, kResidualBlockRows);
-  PCONV_CHECK(bx * by < (int64_t(1) << 31), "launch_residual: too many workgroups for one grid");
+  PCONV_CHECK(bx * by < (int64_t(1) << 31) && bx * by * a.batch < (int64_t(1) << 31),
+              "launch_residual: too many workgroups for one grid (batch x blocks per image)");
   const Taps9 tp = make_taps9(f);
-  const dim3 grid(static_cast<unsigned>(bx * by)), block(64, 4);
+  const dim3 grid(static_cast<unsigned>(bx * by * a.batch)), block(64, 4);
   auto* ctr = reinterpret_cast<unsigned long long*>(counter);
   const int rb = static_cast<int>(a.row_bytes), r0 = static_cast<int>(a.r0), r1 = static_cast<int>(a.r1);
-  const int nbx = static_cast<int>(bx), img_lo = lo, img_hi = hi;
+  const int nbx = static_cast<int>(bx), per_image = static_cast<int>(bx * by), img_lo = lo, img_hi = hi;
+  const int64_t stride = a.batch > 1 ? a.batch_stride : int64_t(0);
   with_bool(!int_form_allowed(f), [&](auto fl) {
     with_bool(a.border == Border::Replicate, [&](auto rep) {
       k_residual<CH, decltype(fl)::value, decltype(rep)::value>
-          <<<grid, block, 0, s>>>(a.src, a.pitch, rb, r0, r1, tp, img_lo, img_hi, nbx, ctr);
+          <<<grid, block, 0, s>>>(a.src, a.pitch, rb, r0, r1, tp, img_lo, img_hi, nbx, per_image, stride, ctr);
     });
   });
 }
@@ -162,7 +179,7 @@ void launch_residual(const Filter& f, Channels ch, const StencilLaunch& a_in, ui
   if (a.r1 <= a.r0) return;
   // Geometry guards: every access of the launch must stay inside the frame.
   PCONV_CHECK(a.row_bytes >= 1, "launch_residual: empty rows");
-  PCONV_CHECK(a.batch == 1, "launch_residual: batch not supported (one image per launch)");
+  check_batch("launch_residual", a);
   check_frame_access("launch_residual", a, a.src && counter, 1);
   PCONV_CHECK(reinterpret_cast<uintptr_t>(a.src) % 16 == 0, "launch_residual: frame rows must be 16-byte aligned");
   PCONV_CHECK(a.row_bytes < (int64_t(1) << 31) - 2048 && a.r1 - a.frame_lo < (int64_t(1) << 31) - 64 &&

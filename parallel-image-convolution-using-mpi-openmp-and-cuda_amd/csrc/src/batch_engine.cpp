@@ -2,6 +2,7 @@
 #include "pconv/batch_engine.hpp"
 
 #include <algorithm>
+#include <cstring>
 #include <string>
 
 #include "pconv/schedule.hpp"
@@ -134,6 +135,143 @@ void BatchEngine::run(int reps, int n) {
     ev_t1_.record(cs_);
     timing_pending_ = true;
   }
+}
+
+// ---- fixed points (BandEngine's pattern, one counter per image) -----------
+
+void BatchEngine::launch_batch_residual(int n) {
+  StencilLaunch a;
+  a.src = frame_at(cur_);
+  a.pitch = lay_.pitch;
+  a.row_bytes = lay_.row_bytes;
+  a.r0 = 0;
+  a.r1 = lay_.rows;
+  a.frame_lo = -lay_.halo;
+  a.frame_hi = lay_.rows + lay_.halo;
+  a.g_row0 = 0;
+  a.height = geom_.height;
+  a.border = opt_.border;
+  a.batch = n;
+  a.batch_stride = stride_;
+  launch_residual(filter_, geom_.channels, a, reinterpret_cast<uint64_t*>(res_count_.data()), cs_);
+}
+
+void BatchEngine::enqueue_residual(int n) {
+  TraceRange tr("pconv.batch.residual");
+  // The host waits for the counts: a check has no place in a graph.
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  PCONV_CHECK(hipStreamIsCapturing(cs_, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone,
+              "BatchEngine: a residual check cannot be enqueued on a capturing stream");
+  const size_t bytes = round_up<size_t>(sizeof(uint64_t) * static_cast<size_t>(capacity_), 16);
+  if (!res_count_.data()) {
+    res_count_ = DeviceBuffer(bytes);
+    res_host_ = PinnedBuffer(bytes);
+    if (opt_.kernel_copies)
+      launch_fill_zero(res_count_.data(), static_cast<int64_t>(bytes), cs_);
+    else
+      PCONV_HIP_CHECK(hipMemsetAsync(res_count_.data(), 0, bytes, cs_));
+    res_ev_ = Event::create();
+    res_seen_.assign(static_cast<size_t>(capacity_), 0);
+  }
+  // The device counters are never zeroed again: they run on, a check is the
+  // per-image difference to the value the check before it read (the stream is
+  // in order).  All `capacity` words are read back: those of images >= n have
+  // not moved.
+  launch_batch_residual(n);
+  if (opt_.kernel_copies)
+    launch_copy_rows(res_count_.data(), static_cast<int64_t>(bytes), res_host_.data(), static_cast<int64_t>(bytes),
+                     static_cast<int64_t>(bytes), 1, cs_);
+  else
+    PCONV_HIP_CHECK(hipMemcpyAsync(res_host_.data(), res_count_.data(), bytes, hipMemcpyDeviceToHost, cs_));
+  res_ev_.record(cs_);
+}
+
+std::vector<uint64_t> BatchEngine::finish_residual(int n) {
+  res_ev_.sync();
+  std::vector<uint64_t> out(static_cast<size_t>(n));
+  for (int b = 0; b < n; ++b) {
+    uint64_t total = 0;
+    std::memcpy(&total, res_host_.data() + sizeof(total) * static_cast<size_t>(b), sizeof(total));
+    out[b] = total - res_seen_[b];
+    res_seen_[b] = total;
+  }
+  return out;
+}
+
+std::vector<uint64_t> BatchEngine::residual(int n) {
+  check_n("BatchEngine::residual", n);
+  if (n == 0) return {};
+  enqueue_residual(n);
+  std::vector<uint64_t> out = finish_residual(n);
+  synchronize();
+  return out;
+}
+
+std::vector<double> BatchEngine::time_residual(int launches, int n) {
+  check_n("BatchEngine::time_residual", n);
+  std::vector<double> ms;
+  if (n == 0) return ms;
+  (void)residual(n);  // the counters exist
+  for (int i = 0; i < launches; ++i) {
+    ev_t0_.record(cs_);
+    launch_batch_residual(n);
+    ev_t1_.record(cs_);
+    PCONV_HIP_CHECK(hipStreamSynchronize(cs_));
+    ms.push_back(Event::elapsed_ms(ev_t0_, ev_t1_));
+  }
+  (void)residual(n);  // (the next check's differences start behind these launches)
+  return ms;
+}
+
+std::vector<StableStats> BatchEngine::run_until_stable(int max_reps, int check_every, int n) {
+  PCONV_CHECK(max_reps >= 0, "repetitions must be >= 0");
+  PCONV_CHECK(check_every >= 1, "check_every must be >= 1");
+  check_n("BatchEngine::run_until_stable", n);
+  std::vector<StableStats> st(static_cast<size_t>(n));
+  if (n == 0) {
+    stats_ = RunStats{};
+    return st;
+  }
+  RunStats sum;
+  const double w0 = wall_seconds();
+  auto chunk = [&](int k) {
+    run(k, n);
+    sum.launches += stats_.launches;
+  };
+  int done = std::min(check_every, max_reps);
+  int checks = 0, open = n;
+  chunk(done);
+  enqueue_residual(n);
+  for (;;) {
+    // The next chunk is enqueued BEFORE the host waits for this check's
+    // counts, so the GPU never idles over the read-back.  If every count turns
+    // out zero, the chunk in flight repeats the fixed points' bytes.
+    const int next = std::min(check_every, max_reps - done);
+    if (next > 0) chunk(next);
+    const std::vector<uint64_t> cnt = finish_residual(n);
+    ++checks;
+    for (int b = 0; b < n; ++b) {
+      StableStats& s = st[b];
+      if (s.converged) {
+        PCONV_CHECK(cnt[b] == 0, "BatchEngine::run_until_stable: image " + std::to_string(b) + " left its fixed point (" +
+                                     std::to_string(cnt[b]) + " bytes change at check " + std::to_string(checks) + ")");
+        continue;
+      }
+      s.residual = cnt[b];
+      s.checks = checks;
+      s.reps_done = done;
+      s.converged = cnt[b] == 0;
+      if (s.converged) --open;
+    }
+    if (open == 0 || next == 0) break;
+    done += next;
+    enqueue_residual(n);
+  }
+  synchronize();
+  sum.wall_ms = (wall_seconds() - w0) * 1e3;
+  sum.loop_ms = sum.wall_ms;  // chunks and checks overlap: the loop is timed as a whole, on the host
+  stats_ = sum;
+  return st;
 }
 
 void BatchEngine::wait_stream(hipStream_t s) {

@@ -465,6 +465,38 @@ PYBIND11_MODULE(_pconv_native, m) {
       py::arg("height") = (int64_t(1) << 40), py::arg("stream") = 0, py::arg("border") = "zero",
       "Residual kernel on a frame (launch_stencil's geometry arguments): bytes of rows [r0, r1) that one more "
       "repetition would change; synchronises the stream.");
+  m.def(
+      "launch_residual_batch",
+      [](py::object filter, const std::string& ch, uintptr_t src, int64_t pitch, int64_t row_bytes, int64_t r0,
+         int64_t r1, int64_t frame_lo, int64_t frame_hi, uintptr_t counters, int batch, int64_t batch_stride,
+         int64_t g_row0, int64_t height, uintptr_t stream, const std::string& border) {
+        StencilLaunch a;
+        a.border = parse_border(border);
+        a.batch = batch;
+        a.batch_stride = batch_stride;
+        a.src = reinterpret_cast<const uint8_t*>(src);
+        a.pitch = pitch;
+        a.row_bytes = row_bytes;
+        a.r0 = r0;
+        a.r1 = r1;
+        a.frame_lo = frame_lo;
+        a.frame_hi = frame_hi;
+        a.g_row0 = g_row0;
+        a.height = height;
+        const Filter f = make_filter(filter);
+        const Channels c = parse_channels(ch);
+        hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+        py::gil_scoped_release nogil;
+        launch_residual(f, c, a, reinterpret_cast<uint64_t*>(counters), s);
+        PCONV_HIP_CHECK(hipStreamSynchronize(s));
+      },
+      py::arg("filter"), py::arg("channels"), py::arg("src"), py::arg("pitch"), py::arg("row_bytes"), py::arg("r0"),
+      py::arg("r1"), py::arg("frame_lo"), py::arg("frame_hi"), py::arg("counters"), py::arg("batch"),
+      py::arg("batch_stride"), py::arg("g_row0") = 0, py::arg("height") = (int64_t(1) << 40), py::arg("stream") = 0,
+      py::arg("border") = "zero",
+      "Residual kernel on `batch` frames batch_stride bytes apart in one launch: image b's count is ADDED to "
+      "counters[b] (a device pointer to at least `batch` uint64 of the caller's, neither zeroed nor read here); "
+      "synchronises the stream.");
   m.attr("RESIDUAL_BLOCK_ROWS") = kResidualBlockRows;
   m.def("set_swar_shape", &set_swar_shape, py::arg("lw") = 0, py::arg("m") = 0, py::arg("nw") = 0,
         "Force the SWAR temporal tile shape (lw=0: back to the latency model).");
@@ -793,6 +825,25 @@ PYBIND11_MODULE(_pconv_native, m) {
       .def("signal_stream", [](BatchEngine& e, uintptr_t s) { e.signal_stream(reinterpret_cast<hipStream_t>(s)); })
       .def("run", &BatchEngine::run, py::arg("reps"), py::arg("n"), py::call_guard<py::gil_scoped_release>())
       .def("synchronize", &BatchEngine::synchronize, py::call_guard<py::gil_scoped_release>())
+      .def("residual", &BatchEngine::residual, py::arg("n"), py::call_guard<py::gil_scoped_release>(),
+           "per-image bytes of the newest frames of images [0, n) that one more repetition would change (one launch)")
+      .def(
+          "run_until_stable",
+          [](BatchEngine& e, int max_reps, int check_every, int n) {
+            std::vector<StableStats> st;
+            {
+              py::gil_scoped_release nogil;
+              st = e.run_until_stable(max_reps, check_every, n);
+            }
+            py::list out;
+            for (const auto& s : st) out.append(py::make_tuple(s.reps_done, s.converged, s.residual, s.checks));
+            return out;
+          },
+          py::arg("max_reps"), py::arg("check_every"), py::arg("n"),
+          "[(reps_done, converged, residual, checks)] of images [0, n), each as a single-image run would report it")
+      .def("time_residual", &BatchEngine::time_residual, py::arg("launches"), py::arg("n"),
+           py::call_guard<py::gil_scoped_release>(),
+           "diagnostics: ms of each of `launches` residual launches over images [0, n) (stream events)")
       .def_property_readonly("stats", &BatchEngine::last_stats);
 
   py::class_<BandPipeline>(m, "BandPipeline")

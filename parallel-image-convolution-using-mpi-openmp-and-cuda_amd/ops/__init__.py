@@ -1,3 +1,4 @@
 """Stencil operators: native HIP/CPU dispatch and the NumPy oracle."""
 from .stencil import Engine, StableInfo, convolve, convolve_until_stable, image_geometry, residual  # noqa: F401
+from .stencil import BatchEngine, convolve_batch, convolve_batch_until_stable, residual_batch  # noqa: F401
 from .reference import numpy_convolve, numpy_residual, numpy_step  # noqa: F401

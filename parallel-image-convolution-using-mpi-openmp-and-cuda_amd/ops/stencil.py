@@ -351,6 +351,7 @@ class BatchEngine:
                                   variant=variant, border=self.border)
         self.capacity = self._eng.capacity
         self.row_bytes = self._eng.row_bytes
+        self._n = 0  # images of the last call (residual(None) counts those)
 
     @property
     def fuse(self) -> int:
@@ -368,39 +369,79 @@ class BatchEngine:
             raise ValueError(f"{shape[0]} images exceed the engine's capacity {self.capacity}")
         return shape[0]
 
-    def run_numpy(self, stack: np.ndarray, reps: int) -> np.ndarray:
+    def _with_frames_numpy(self, stack: np.ndarray, work):
+        """Upload the stack, ``work(n)`` on the resident frames, download the
+        newest frames: ``(out, work's result)`` (``None`` for an empty stack)."""
         src = np.ascontiguousarray(stack, dtype=np.uint8)
-        n = self._check_stack(src.shape)
+        n = self._n = self._check_stack(src.shape)
         out = np.empty_like(src)
         if n == 0:
-            return out
+            return out, None
         self._eng.upload(src.reshape(-1), n)
-        self._eng.run(int(reps), n)
+        res = work(n)
         self._eng.download(out.reshape(-1), n)
         self._eng.synchronize()
-        return out
+        return out, res
 
-    def run_tensor(self, stack: torch.Tensor, reps: int) -> torch.Tensor:
+    def _with_frames_tensor(self, stack: torch.Tensor, work):
         if stack.device.type != "cuda":
-            return torch.from_numpy(self.run_numpy(stack.numpy(), reps))
+            out, res = self._with_frames_numpy(stack.numpy(), work)
+            return torch.from_numpy(out), res
         src = stack.contiguous()
-        n = self._check_stack(src.shape)
+        n = self._n = self._check_stack(src.shape)
         out = torch.empty_like(src)
         if n == 0:
-            return out
+            return out, None
         ts = torch.cuda.current_stream(src.device).cuda_stream
         self._eng.wait_stream(ts)
         self._eng.upload_ptr(src.data_ptr(), n, device=True)
-        self._eng.run(int(reps), n)
+        res = work(n)
         self._eng.download_ptr(out.data_ptr(), n, device=True)
         self._eng.signal_stream(ts)
         src.record_stream(torch.cuda.current_stream(src.device))
-        return out
+        return out, res
+
+    def _with_frames(self, stack, work):
+        if isinstance(stack, torch.Tensor):
+            return self._with_frames_tensor(stack, work)
+        return self._with_frames_numpy(np.asarray(stack), work)
+
+    def run_numpy(self, stack: np.ndarray, reps: int) -> np.ndarray:
+        return self._with_frames_numpy(stack, lambda n: self._eng.run(int(reps), n))[0]
+
+    def run_tensor(self, stack: torch.Tensor, reps: int) -> torch.Tensor:
+        return self._with_frames_tensor(stack, lambda n: self._eng.run(int(reps), n))[0]
 
     def __call__(self, stack, reps: int):
         if isinstance(stack, torch.Tensor):
             return self.run_tensor(stack, reps)
         return self.run_numpy(np.asarray(stack), reps)
+
+    # ---- fixed points ------------------------------------------------
+    def residual(self, stack=None) -> np.ndarray:
+        """Per image, the bytes one more repetition would change, ``(n,)``
+        int64 from one launch: of the images of ``stack``, or (``None``) of the
+        frames the engine holds after its last call, for that call's ``n``."""
+        if stack is None:
+            res = self._eng.residual(self._n) if self._n else []
+        else:
+            res = self._with_frames(stack, self._eng.residual)[1] or []
+        return np.asarray(res, dtype=np.int64).reshape(-1)
+
+    def run_until_stable(self, stack, max_reps: int, check_every: Optional[int] = None):
+        """All images of ``stack`` in chunks of ``check_every`` repetitions
+        (default 16 x fuse) with a per-image residual check after each, until
+        every image is at its fixed point or at ``max_reps``.  Returns ``(out,
+        [StableInfo] * n)``: ``out[b]`` and entry b are what a single-image run
+        of image b returns (an image that converged at an earlier check than
+        the rest went on rewriting the same bytes)."""
+        if max_reps < 0:
+            raise ValueError("max_reps must be >= 0")
+        k = _GPU_CHECK_LAUNCHES * self.fuse if check_every is None else int(check_every)
+        if k < 1:
+            raise ValueError("check_every must be >= 1")
+        out, st = self._with_frames(stack, lambda n: self._eng.run_until_stable(int(max_reps), k, n))
+        return out, [StableInfo(int(s[0]), bool(s[1]), int(s[2]), int(s[3])) for s in (st or [])]
 
 
 # convolve_batch's own engine cache (the single-image engines keep theirs).
@@ -460,6 +501,48 @@ def _as_stack(images):
     return np.stack(arrs), False
 
 
+def _prepare_batch(images, filter, backend, border, batch_size):
+    """The argument checks the batch entry points share: (filter, stack,
+    is_tensor, (width, height, channels), resolved backend)."""
+    if batch_size is not None and int(batch_size) < 1:
+        raise ValueError("batch_size must be >= 1")
+    flt = get_filter(filter)
+    check_border(border)
+    stack, is_tensor = _as_stack(images)
+    shape = tuple(int(s) for s in stack.shape)
+    if len(shape) not in (3, 4):
+        raise ValueError(f"unsupported batch shape {shape}: expected (N, H, W) or (N, H, W, 1|3|4)")
+    geo = image_geometry(shape[1:])
+    if backend == "auto":
+        backend = "hip" if (is_tensor and stack.is_cuda) else _default_backend()
+    if backend not in ("hip", "omp", "cpu", "numpy"):
+        raise ValueError(f"unknown backend {backend!r} (hip|omp|cpu|numpy|auto)")
+    return flt, stack, is_tensor, geo, backend
+
+
+def _empty_like_stack(stack, is_tensor):
+    return torch.empty_like(stack) if is_tensor else np.empty(tuple(stack.shape), dtype=np.uint8)
+
+
+def _hip_batch_engine(stack, is_tensor, geo, flt, device, fuse, variant, border, batch_size):
+    """The cached BatchEngine for a stack and its capacity (the chunk size)."""
+    n = require_native()
+    w, h, ch = geo
+    n_img = int(stack.shape[0])
+    if device is None:
+        device = stack.device.index if (is_tensor and stack.is_cuda) else 0
+    device = int(device or 0)
+    if fuse is None:
+        c = {"grey": 1, "rgb": 3, "rgba": 4}[ch]
+        fuse = n.auto_fuse(flt.to_native(), variant, w * h * c, c)
+    fuse = int(fuse)
+    if batch_size is None:
+        cap = max(1, min(n_img, _BATCH_BYTES // (2 * _frame_bytes(w, h, ch, fuse))))
+    else:
+        cap = min(n_img, int(batch_size))
+    return _cached_batch_engine(w, h, ch, cap, flt, device, fuse, variant, border), cap
+
+
 def convolve_batch(images, reps: int = 1, filter="gaussian", backend: str = "auto", device: Optional[int] = None,
                    fuse: Optional[int] = None, variant: str = "auto", threads: int = 0, border: str = "zero",
                    batch_size: Optional[int] = None):
@@ -479,45 +562,75 @@ def convolve_batch(images, reps: int = 1, filter="gaussian", backend: str = "aut
     """
     if reps < 0:
         raise ValueError("reps must be >= 0")
-    if batch_size is not None and int(batch_size) < 1:
-        raise ValueError("batch_size must be >= 1")
-    flt = get_filter(filter)
-    check_border(border)
-    stack, is_tensor = _as_stack(images)
-    shape = tuple(int(s) for s in stack.shape)
-    if len(shape) not in (3, 4):
-        raise ValueError(f"unsupported batch shape {shape}: expected (N, H, W) or (N, H, W, 1|3|4)")
-    w, h, ch = image_geometry(shape[1:])
-    n_img = shape[0]
-    is_cuda = is_tensor and stack.is_cuda
-    if backend == "auto":
-        backend = "hip" if is_cuda else _default_backend()
-    if backend not in ("hip", "omp", "cpu", "numpy"):
-        raise ValueError(f"unknown backend {backend!r} (hip|omp|cpu|numpy|auto)")
+    flt, stack, is_tensor, geo, backend = _prepare_batch(images, filter, backend, border, batch_size)
+    n_img = int(stack.shape[0])
     if n_img == 0:
-        return torch.empty_like(stack) if is_tensor else np.empty(shape, dtype=np.uint8)
+        return _empty_like_stack(stack, is_tensor)
 
     if backend != "hip":
         outs = [convolve(stack[i], reps, flt, backend=backend, threads=threads, border=border) for i in range(n_img)]
         return torch.stack(outs) if is_tensor else np.stack(outs)
 
-    n = require_native()
-    if device is None:
-        device = stack.device.index if is_cuda else 0
-    device = int(device or 0)
-    if fuse is None:
-        c = {"grey": 1, "rgb": 3, "rgba": 4}[ch]
-        fuse = n.auto_fuse(flt.to_native(), variant, w * h * c, c)
-    fuse = int(fuse)
-    if batch_size is None:
-        cap = max(1, min(n_img, _BATCH_BYTES // (2 * _frame_bytes(w, h, ch, fuse))))
-    else:
-        cap = min(n_img, int(batch_size))
-    eng = _cached_batch_engine(w, h, ch, cap, flt, device, fuse, variant, border)
+    eng, cap = _hip_batch_engine(stack, is_tensor, geo, flt, device, fuse, variant, border, batch_size)
     if n_img <= cap:
         return eng(stack, reps)
     outs = [eng(stack[i:i + cap], reps) for i in range(0, n_img, cap)]
     return torch.cat(outs) if is_tensor else np.concatenate(outs)
+
+
+def convolve_batch_until_stable(images, max_reps: int, filter="gaussian", check_every: Optional[int] = None,
+                                backend: str = "auto", device: Optional[int] = None, fuse: Optional[int] = None,
+                                variant: str = "auto", threads: int = 0, border: str = "zero",
+                                batch_size: Optional[int] = None):
+    """``convolve_until_stable`` for N same-size 8-bit images at once.
+
+    Inputs, backends, the engine cache and ``batch_size`` are
+    :func:`convolve_batch`'s.  Returns ``(stack, [StableInfo] * N)`` where, on
+    every backend and for every b, ``stack[b]`` and entry b equal what
+    ``convolve_until_stable(images[b], max_reps, filter, check_every, ...)``
+    returns.  On the ``hip`` backend the images of a chunk advance together and
+    every check counts all of them in one launch of the residual kernel; a
+    chunk's loop ends when its last image has converged (the others rewrite
+    their fixed point's bytes meanwhile) or at ``max_reps``.  The other
+    backends loop over the images.
+    """
+    if max_reps < 0:
+        raise ValueError("max_reps must be >= 0")
+    if check_every is not None and int(check_every) < 1:
+        raise ValueError("check_every must be >= 1")
+    flt, stack, is_tensor, geo, backend = _prepare_batch(images, filter, backend, border, batch_size)
+    n_img = int(stack.shape[0])
+    if n_img == 0:
+        return _empty_like_stack(stack, is_tensor), []
+
+    if backend != "hip":
+        res = [convolve_until_stable(stack[i], max_reps, flt, check_every=check_every, backend=backend,
+                                     threads=threads, border=border) for i in range(n_img)]
+        outs = [r[0] for r in res]
+        return (torch.stack(outs) if is_tensor else np.stack(outs)), [r[1] for r in res]
+
+    eng, cap = _hip_batch_engine(stack, is_tensor, geo, flt, device, fuse, variant, border, batch_size)
+    if n_img <= cap:
+        return eng.run_until_stable(stack, int(max_reps), check_every)
+    res = [eng.run_until_stable(stack[i:i + cap], int(max_reps), check_every) for i in range(0, n_img, cap)]
+    outs = [r[0] for r in res]
+    return (torch.cat(outs) if is_tensor else np.concatenate(outs)), [info for r in res for info in r[1]]
+
+
+def residual_batch(images, filter="gaussian", backend: str = "auto", device: Optional[int] = None, threads: int = 0,
+                   border: str = "zero") -> np.ndarray:
+    """:func:`residual` of N same-size images, ``(N,)`` int64: equals
+    ``[residual(img, ...) for img in images]``; on the ``hip`` backend one
+    launch of the residual kernel per chunk of the batch engine."""
+    flt, stack, is_tensor, geo, backend = _prepare_batch(images, filter, backend, border, None)
+    n_img = int(stack.shape[0])
+    if n_img == 0:
+        return np.zeros((0,), dtype=np.int64)
+    if backend != "hip":
+        return np.asarray([residual(stack[i], flt, backend=backend, threads=threads, border=border)
+                           for i in range(n_img)], dtype=np.int64)
+    eng, cap = _hip_batch_engine(stack, is_tensor, geo, flt, device, None, "auto", border, None)
+    return np.concatenate([eng.residual(stack[i:i + cap]) for i in range(0, n_img, cap)])
 
 
 def convolve_file(path: str, width: int, height: int, reps: int, channels: str = "grey", filter="gaussian",
