@@ -29,6 +29,7 @@ from ._native import native, native_available  # noqa: E402  (loads torch first)
 from .models.filters import Filter, get_filter, list_filters  # noqa: E402
 from .ops.stencil import convolve, convolve_file, convolve_until_stable, residual, Engine, StableInfo  # noqa: E402
 from .ops.stencil import BatchEngine, convolve_batch, convolve_batch_until_stable, residual_batch  # noqa: E402
+from .ops.stencil import convolve_many, convolve_many_until_stable, residual_many, size_buckets  # noqa: E402
 from .models.pipeline import FilterPipeline  # noqa: E402
 from .ops.reference import numpy_convolve, numpy_residual  # noqa: E402
 from .utils.raw_io import read_raw, write_raw, output_path_for, synthetic_image  # noqa: E402
@@ -46,6 +47,10 @@ __all__ = [
     "convolve_batch",
     "convolve_batch_until_stable",
     "residual_batch",
+    "convolve_many",
+    "convolve_many_until_stable",
+    "residual_many",
+    "size_buckets",
     "FilterPipeline",
     "numpy_convolve",
     "residual",

@@ -16,9 +16,17 @@
 // reported.  Converged images keep advancing with the rest (they rewrite the
 // same bytes) until the last image converges or max_reps is reached.
 //
+// Mixed sizes: the engine's geometry is then an ENVELOPE.  upload_sized puts
+// images of any sizes within it top-left into their frames and hands every
+// launch a table of their extents (StencilLaunch::dims): each image is
+// convolved as a lone image of its own size, in the same ceil(reps / fuse)
+// launches.  No frame is cleared in between — the kernels read nothing outside
+// an image, so a larger image's stale bytes never leak.  The mode lasts until
+// the next plain upload().
+//
 // Out of scope here (see docs/ARCHITECTURE.md §5): hipGraph capture, retiring
-// converged images from the launches (compaction), images of different sizes,
-// more than one GPU.
+// converged images from the launches (compaction), more than one GPU; and for
+// mixed sizes the CLI, the service and the pipelines.
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -33,6 +41,19 @@
 #include "pconv/kernels.hpp"
 
 namespace pconv {
+
+// One image of a mixed-size upload, in pixels.
+struct ImageSize {
+  int64_t width = 0;
+  int64_t height = 0;
+};
+
+// The host half of upload_sized, free of any device call: the extents table of
+// `sizes` inside the envelope `env` for an engine of `capacity` frames
+// (throws when there are too many images or one does not fit), and the bytes
+// of the packed buffer that holds them back to back with tight rows.
+std::vector<ImageDims> image_dims_table(const ImageGeom& env, int capacity, const std::vector<ImageSize>& sizes);
+int64_t packed_bytes(const ImageGeom& env, const std::vector<ImageSize>& sizes);
 
 class BatchEngine {
  public:
@@ -59,6 +80,18 @@ class BatchEngine {
   // memory.
   void upload(const uint8_t* p, int n, bool device = false);
   void download(uint8_t* p, int n, bool device = false);
+  // Mixed sizes: `p` holds sizes.size() <= capacity images back to back with
+  // tight rows, image b as sizes[b].height rows of sizes[b].width x channels
+  // bytes, each within the engine's geometry (the envelope).  One pitched 2-D
+  // copy per image, and the extents table goes to the device on the same
+  // stream.  From here on run / residual / run_until_stable / time_residual
+  // take n == sizes.size() and treat every image as a lone one of its size;
+  // download_sized returns the newest frames' image regions in the same
+  // packing.  The next plain upload() ends the mode.
+  void upload_sized(const uint8_t* p, const std::vector<ImageSize>& sizes, bool device = false);
+  void download_sized(uint8_t* p, bool device = false);
+  // Sizes of the current mixed-size upload (empty: uniform launches).
+  const std::vector<ImageSize>& sizes() const { return sizes_; }
   // Enqueue `reps` repetitions of images [0, n) (async).
   void run(int reps, int n);
 
@@ -87,6 +120,7 @@ class BatchEngine {
 
  private:
   void check_n(const char* who, int n) const;
+  void set_dims(StencilLaunch& a) const;
   void launch_batch_residual(int n);
   void enqueue_residual(int n);
   std::vector<uint64_t> finish_residual(int n);
@@ -103,6 +137,14 @@ class BatchEngine {
   PinnedBuffer res_host_;           // pinned words the running counts are read back into
   Event res_ev_;                    // the latest read-back has landed
   std::vector<uint64_t> res_seen_;  // the running counts at the latest check read
+  // Mixed sizes: the extents of the current upload_sized (empty: uniform), the
+  // pinned words they are copied out of, the device table of `capacity`
+  // entries (allocated on first use), and the event behind the latest copy.
+  std::vector<ImageSize> sizes_;
+  std::vector<ImageDims> dims_host_;
+  PinnedBuffer dims_pin_;
+  DeviceBuffer dims_dev_;
+  Event dims_ev_;
   Stream own_cs_;
   hipStream_t cs_ = nullptr;
   Event ev_t0_, ev_t1_, ev_sync_;

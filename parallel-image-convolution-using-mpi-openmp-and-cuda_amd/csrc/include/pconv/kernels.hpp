@@ -29,6 +29,13 @@
 
 namespace pconv {
 
+// Extent of one image of a mixed-size batch inside its frame (device table of
+// the temporal and residual kernels, host copy for the guards): 8 bytes.
+struct ImageDims {
+  int32_t row_bytes;
+  int32_t height;
+};
+
 struct StencilLaunch {
   const uint8_t* src = nullptr;  // frame: owned row 0, data column 0
   uint8_t* dst = nullptr;        // same layout as src
@@ -51,6 +58,19 @@ struct StencilLaunch {
   // read each other's rows: the batch only moves the base pointers.
   int batch = 1;
   int64_t batch_stride = 0;
+  // Mixed sizes (temporal kernels and the residual kernel): every field above
+  // is then the ENVELOPE all frames share, and image b occupies rows
+  // [0, dims[b].height) and bytes [0, dims[b].row_bytes) of its frame, top-left
+  // aligned.  It is convolved exactly as a lone image of that size under
+  // either border: whatever the rest of its frame holds (pad columns, ghost
+  // rows, a larger image's stale bytes) reads as out-of-image, and nothing of
+  // the destination frame outside the image is written.  `dims` is device
+  // memory of `batch` entries (the kernels clamp each entry to the envelope),
+  // `dims_host` the host copy of the same entries the guards read; both or
+  // neither.  Null: every image is the envelope.  Whole images only
+  // (g_row0 = 0, r0 = 0, r1 = height); batch = 1 is allowed.
+  const ImageDims* dims = nullptr;
+  const ImageDims* dims_host = nullptr;
 };
 
 enum class KernelVariant : int {
@@ -161,8 +181,9 @@ void set_float_shape(int m, int nw);
 // Forget the tuned shapes: of both kernels, of the float kernel alone.
 void clear_swar_tuning();
 void clear_float_tuning();
-// Tuned SWAR entries: ({channels, steps, rows, row_bytes, step_form, kernel, batch}, shape); kernel 0: the
-// tile kernel k_swar, 1: the buffer-op tile kernel k_swar_pf.
+// Tuned SWAR entries: ({channels, steps, rows, row_bytes, step_form, kernel, batch, live}, shape); kernel 0: the
+// tile kernel k_swar, 1: the buffer-op tile kernel k_swar_pf; live: the workgroups of a mixed-size launch
+// (StencilLaunch::dims) that have output in their image, 0 for a uniform launch.
 std::vector<std::pair<std::vector<int64_t>, SwarShape>> swar_tuned();
 
 }  // namespace pconv

@@ -105,7 +105,8 @@ template <int CH, bool FLOAT, bool REP>
 __global__ __launch_bounds__(256) void k_residual(const uint8_t* __restrict__ src, int64_t pitch, int row_bytes,
                                                   int r0, int r1, Taps9 tp, int img_lo, int img_hi, int blocks_x,
                                                   int blocks_per_image, int64_t batch_stride,
-                                                  unsigned long long* __restrict__ counter) {
+                                                  unsigned long long* __restrict__ counter,
+                                                  const ImageDims* __restrict__ dims) {
   __shared__ u32 part[4];
   // Image of the batch: from the workgroup id (scalar); it only moves the
   // frame pointer and picks the counter.
@@ -114,6 +115,18 @@ __global__ __launch_bounds__(256) void k_residual(const uint8_t* __restrict__ sr
   src += static_cast<int64_t>(img) * batch_stride;
   const int bx = static_cast<int>(blk % static_cast<unsigned>(blocks_x));
   const int by = static_cast<int>(blk / static_cast<unsigned>(blocks_x));
+  // Mixed sizes: the image's own extent replaces the envelope's (one scalar
+  // load; img is workgroup-uniform; whole images, so r0 = img_lo = 0).  The
+  // min keeps a wrong table inside the frame.  A workgroup of the envelope's
+  // grid with no byte of this image adds nothing: gone before its first load
+  // and the barrier, no atomic.
+  if (dims != nullptr) {
+    const ImageDims d = dims[img];
+    row_bytes = min(d.row_bytes, row_bytes);
+    img_hi = min(d.height, img_hi);
+    r1 = min(d.height, r1);
+    if (bx * 1024 >= row_bytes || r0 + by * 4 * kRpt >= r1) return;
+  }
   const int x = (bx * 64 + static_cast<int>(threadIdx.x)) * 16;
   const int rs = r0 + (by * 4 + static_cast<int>(threadIdx.y)) * kRpt;
   u32 cnt = 0;
@@ -164,7 +177,8 @@ void launch_ch(const Filter& f, const StencilLaunch& a, uint64_t* counter, hipSt
   with_bool(!int_form_allowed(f), [&](auto fl) {
     with_bool(a.border == Border::Replicate, [&](auto rep) {
       k_residual<CH, decltype(fl)::value, decltype(rep)::value>
-          <<<grid, block, 0, s>>>(a.src, a.pitch, rb, r0, r1, tp, img_lo, img_hi, nbx, per_image, stride, ctr);
+          <<<grid, block, 0, s>>>(a.src, a.pitch, rb, r0, r1, tp, img_lo, img_hi, nbx, per_image, stride, ctr,
+                                  a.dims);
     });
   });
 }
@@ -173,6 +187,7 @@ void launch_ch(const Filter& f, const StencilLaunch& a, uint64_t* counter, hipSt
 
 void launch_residual(const Filter& f, Channels ch, const StencilLaunch& a_in, uint64_t* counter, hipStream_t stream) {
   StencilLaunch a = a_in;
+  check_dims("launch_residual", a, channel_count(ch));  // on the rows as given: whole images
   // rows outside the global image are no part of the map (launch_stencil's clip)
   a.r0 = std::max(a.r0, -a.g_row0);
   a.r1 = std::min(a.r1, a.height - a.g_row0);

@@ -267,7 +267,7 @@ template <int CH, bool UNIFORM, int M, int NW, bool REP = false>
 __global__ __launch_bounds__(64 * NW) void k_float_temporal(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
                                                             int64_t pitch, int row_bytes, int r0, int r1, int steps,
                                                             int g_row0, int height, FloatTaps tp,
-                                                            int64_t batch_stride) {
+                                                            int64_t batch_stride, const ImageDims* __restrict__ dims) {
   __shared__ uint2 lds[2][NW][2][64];  // [parity][wave][top/bottom][lane]
   // Image of the batch: grid.z (scalar); it only moves the two base pointers.
   // The empty asm settles both sums here, in scalar registers: from this line
@@ -276,6 +276,25 @@ __global__ __launch_bounds__(64 * NW) void k_float_temporal(const uint8_t* __res
   src += static_cast<int64_t>(blockIdx.z) * batch_stride;
   dst += static_cast<int64_t>(blockIdx.z) * batch_stride;
   asm volatile("" : "+s"(src), "+s"(dst));
+  // Mixed sizes: the image's own extent replaces the envelope's (one scalar
+  // load; blockIdx.z is workgroup-uniform).  The min keeps a wrong table inside
+  // the frame.  Everything below reads the two values as it reads the arguments.
+  if (dims != nullptr) {
+    const ImageDims d = dims[blockIdx.z];
+    row_bytes = min(d.row_bytes, row_bytes);
+    height = min(d.height, height);
+    // A tile of the envelope's grid with no output in this image: gone before
+    // its first load and before any barrier (workgroup-uniform: every wave of
+    // the workgroup ends here).  The wave ends in an opaque asm, not a
+    // `return`: with a second exit in its control flow the compiler gave the
+    // uniform 16-row replicate instantiations one VGPR more, and
+    // <1, true, 16, {4, 8}, true> went from 128 to 129 and lost a wave; so
+    // written, all 60 instantiations keep their registers (PERFORMANCE.md 3.5).
+    const int vl = 64 - 2 * ((steps * CH + 7) >> 3);
+    if (static_cast<int>(blockIdx.x) * vl * 8 >= row_bytes ||
+        r0 + static_cast<int>(blockIdx.y) * (NW * M - 2 * steps) + g_row0 >= height)
+      asm volatile("s_endpgm" ::: "memory");
+  }
   const int lane = threadIdx.x & 63;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int hl = (steps * CH + 7) >> 3;  // halo lanes per side
@@ -497,7 +516,7 @@ void launch_ft_shape(const StencilLaunch& a, const FloatTaps& tp, hipStream_t s)
   kern<<<grid, dim3(64 * NW), 0, s>>>(
       a.src, a.dst, a.pitch, static_cast<int>(a.row_bytes), static_cast<int>(a.r0), static_cast<int>(a.r1), a.steps,
       static_cast<int>(a.g_row0), static_cast<int>(std::min<int64_t>(a.height, int64_t(1) << 30)), tp,
-      a.batch > 1 ? a.batch_stride : int64_t(0));
+      a.batch > 1 ? a.batch_stride : int64_t(0), a.dims);
 }
 
 template <int CH, bool UNIFORM>
@@ -512,7 +531,8 @@ void launch_ft_with(const StencilLaunch& a, const FloatTaps& tp, hipStream_t s, 
 // Empirical shape tuning, as for the SWAR kernel (stencil_swar.hip): on the
 // first launch of a geometry every shape that runs it is timed on the REAL
 // launch (fastest_candidate, tuning.hpp) and the fastest is cached per
-// (channels, uniform, steps, rows, row bytes, batch).  The
+// (channels, uniform, steps, rows, row bytes, batch, live workgroups of a
+// mixed-size launch under the model's shape; 0: uniform).  The
 // shape is a large lever on these small frames and not monotonic in the
 // model (1920x2520 RGB box, 4 steps: 8.0 us/rep with 16x8 tiles, 9.2-10.4
 // with the others; gpurun_out/r03/g/float_sweep.jsonl).  Never while the
@@ -523,9 +543,10 @@ struct FtKey {
   int steps;
   int64_t rows, row_bytes;
   int batch;
+  int64_t live;
   bool operator<(const FtKey& o) const {
-    return std::tie(ch, uniform, steps, rows, row_bytes, batch) <
-           std::tie(o.ch, o.uniform, o.steps, o.rows, o.row_bytes, o.batch);
+    return std::tie(ch, uniform, steps, rows, row_bytes, batch, live) <
+           std::tie(o.ch, o.uniform, o.steps, o.rows, o.row_bytes, o.batch, o.live);
   }
 };
 std::mutex g_ft_mu;
@@ -536,7 +557,10 @@ FloatShape tuned_ft_shape(const StencilLaunch& a, const FloatTaps& tp, hipStream
   const int64_t rows = a.r1 - a.r0;
   const FloatShape model = pick_ft_shape(a.steps, CH, rows, a.row_bytes, a.batch);
   if (g_ft_force_m.load(std::memory_order_relaxed) || !shape_tuning_enabled()) return model;
-  const FtKey key{CH, UNIFORM, a.steps, rows, a.row_bytes, a.batch};
+  // (the model saw the envelope: an early-exiting workgroup is charged as a full one)
+  const FtGeom mg = ft_geom(model, CH, a.steps, rows, a.row_bytes, a.batch);
+  const FtKey key{CH, UNIFORM, a.steps, rows, a.row_bytes, a.batch,
+                  live_workgroups(a, int64_t(mg.vlanes) * 8, mg.vrows, 1)};
   {
     std::lock_guard<std::mutex> lk(g_ft_mu);
     auto it = g_ft_tuned.find(key);
@@ -565,6 +589,7 @@ void float_temporal(const Filter& f, Channels ch, const StencilLaunch& a, hipStr
   PCONV_CHECK(a.height < (int64_t(1) << 30) && a.g_row0 < (int64_t(1) << 30), "float temporal kernel: rows exceed 2^30");
   PCONV_CHECK(a.row_bytes > 0 && a.row_bytes < (int64_t(1) << 30), "float temporal kernel: row bytes out of range");
   check_batch("launch_float_temporal", a);
+  check_dims("launch_float_temporal", a, channel_count(ch));
   PCONV_CHECK(a.batch <= 65535, "launch_float_temporal: batch " + std::to_string(a.batch) + " exceeds grid.z (65535)");
   FloatTaps tp;
   bool uniform = true;

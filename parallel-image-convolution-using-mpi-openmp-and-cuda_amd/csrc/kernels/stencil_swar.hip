@@ -112,12 +112,26 @@ __device__ __forceinline__ void edge_fix(EdgeFix<CH, NP, true>& ef, int baseA, i
 template <int CH, int NP, int M>
 __device__ __forceinline__ void edge_fix(EdgeFix<CH, NP, false>&, int, int, bool, int, int, int, int, int) {}
 
+// A chunk with the bytes from `valid` on zeroed.
+template <int NP>
+__device__ __forceinline__ typename Chunk<NP>::T mask_chunk(typename Chunk<NP>::T v, int valid) {
+  if constexpr (NP == 8) {
+    if (valid < 8) {
+      v.x &= valid >= 4 ? 0xffffffffu : ((1u << (8 * valid)) - 1u);
+      v.y &= valid <= 4 ? 0u : ((1u << (8 * (valid - 4))) - 1u);
+    }
+  } else {
+    if (valid < 4) v &= (1u << (8 * valid)) - 1u;
+  }
+  return v;
+}
+
 template <int CH, int LW, int M, int NW, int FORM, bool REP = false>
 __global__ __launch_bounds__(64 * NW) void k_swar(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
                                                   int64_t pitch, int row_bytes, int r0, int r1,
                                                   int steps, int g_row0, int height, int nstrips, int pair_stride,
                                                   int row_tiles, int xcd_swizzle, int tiles_per_image,
-                                                  int64_t batch_stride) {
+                                                  int64_t batch_stride, const ImageDims* __restrict__ dims) {
   constexpr int NP = LW;       // pairs per row per lane
   constexpr int NQ = NP / 4;   // uint4 per row per lane
   using CT = typename Chunk<NP>::T;
@@ -146,6 +160,18 @@ __global__ __launch_bounds__(64 * NW) void k_swar(const uint8_t* __restrict__ sr
     tile -= img * tiles_per_image;
     src += static_cast<int64_t>(img) * batch_stride;
     dst += static_cast<int64_t>(img) * batch_stride;
+    // Mixed sizes: the image's own extent replaces the envelope's (one scalar
+    // load; img is workgroup-uniform).  The min keeps a wrong table inside the
+    // frame.  Everything below reads the two values as it reads the arguments.
+    if (dims != nullptr) {
+      const ImageDims d = dims[img];
+      row_bytes = min(d.row_bytes, row_bytes);
+      height = min(d.height, height);
+      // A tile of the envelope's grid with no output in this image: gone
+      // before its first load and before any barrier (workgroup-uniform).
+      const int col0 = tile / row_tiles;
+      if (col0 * vbytes >= row_bytes || r0 + (tile - col0 * row_tiles) * (NW * M - 2 * steps) + g_row0 >= height) return;
+    }
   }
   const int col = tile / row_tiles, rtile = tile - col * row_tiles;
   const int sA = col, sB = col + pair_stride;
@@ -173,7 +199,14 @@ __global__ __launch_bounds__(64 * NW) void k_swar(const uint8_t* __restrict__ sr
     const uint8_t* rowp = src + static_cast<int64_t>(fr) * pitch;
     if (rok && validA > 0) a = *reinterpret_cast<const CT*>(rowp + xA);
     if (rok && validB > 0) b = *reinterpret_cast<const CT*>(rowp + xB);
-    unpack<NP>(a, b, D[i]);
+    // The row's last chunk is loaded whole and cut to its valid bytes: what
+    // follows an image's row is the zero pad only when the image is the
+    // envelope (mixed sizes: possibly a larger image's stale bytes).  The cut
+    // stands here, where the chunk is consumed, and not in the branches that
+    // load it: there every load waited for its own data before the next one
+    // was issued (1920x630 grey, tile {4,4,8}: 48.7 -> 58.0 us per 40
+    // repetitions; PERFORMANCE.md 3.5).
+    unpack<NP>(mask_chunk<NP>(a, validA), mask_chunk<NP>(b, validB), D[i]);
   }
   const int out_top = min(max(-g_row0 - row_base, 0), M);
   const int out_bot = min(max(height - g_row0 - row_base, 0), M);
@@ -229,7 +262,7 @@ __global__ __launch_bounds__(64 * NW) void k_swar_pf(const uint8_t* __restrict__
                                                      int pitch, int row_bytes, int r0, int r1,
                                                      int steps, int g_row0, int height, int nstrips, int pair_stride,
                                                      int row_tiles, int xcd_swizzle, int tiles_per_image,
-                                                     int64_t batch_stride) {
+                                                     int64_t batch_stride, const ImageDims* __restrict__ dims) {
   constexpr int LW = 4, NP = 4, NQ = 1;
   constexpr u32 kOut = 0x80000000u;  // offset past every descriptor's range
   __shared__ uint4 lds[2][NW][2][NQ][64];
@@ -238,9 +271,6 @@ __global__ __launch_bounds__(64 * NW) void k_swar_pf(const uint8_t* __restrict__
   const int hl = (steps * CH + LW - 1) / LW;
   const int vbytes = (64 - 2 * hl) * LW;
   const int vrows = NW * M - 2 * steps;
-  // Source rows [lo_ok, hi_ok) are readable; destination rows [r0, st_end).
-  const int lo_ok = max(r0 - steps, -g_row0), hi_ok = min(r1 + steps, height - g_row0);
-  const int st_end = min(r1, height - g_row0);
   // XCD-aware tile order over the whole batch (as k_swar): each XCD gets one
   // contiguous run of tiles walked down a column strip, so vertically adjacent
   // tiles (which read each other's halo rows) share an L2.  The image's own
@@ -251,12 +281,25 @@ __global__ __launch_bounds__(64 * NW) void k_swar_pf(const uint8_t* __restrict__
     const int q = nwg >> 3, rem = nwg & 7, xcd = tile & 7, local = tile >> 3;
     tile = xcd * q + min(xcd, rem) + local;
   }
-  {
-    const int img = tile / tiles_per_image;
-    tile -= img * tiles_per_image;
-    src += static_cast<int64_t>(img) * batch_stride;
-    dst += static_cast<int64_t>(img) * batch_stride;
+  const int img = tile / tiles_per_image;
+  tile -= img * tiles_per_image;
+  // Mixed sizes: the image's own extent replaces the envelope's (one scalar
+  // load; img is workgroup-uniform; whole dwords per row are the launch's
+  // contract per image).  The min keeps a wrong table inside the frame.
+  if (dims != nullptr) {
+    const ImageDims d = dims[img];
+    row_bytes = min(d.row_bytes, row_bytes);
+    height = min(d.height, height);
+    // A tile of the envelope's grid with no output in this image: gone before
+    // its first load and before any barrier (workgroup-uniform).
+    const int col0 = tile / row_tiles;
+    if (col0 * vbytes >= row_bytes || r0 + (tile - col0 * row_tiles) * vrows + g_row0 >= height) return;
   }
+  // Source rows [lo_ok, hi_ok) are readable; destination rows [r0, st_end).
+  const int lo_ok = max(r0 - steps, -g_row0), hi_ok = min(r1 + steps, height - g_row0);
+  const int st_end = min(r1, height - g_row0);
+  src += static_cast<int64_t>(img) * batch_stride;
+  dst += static_cast<int64_t>(img) * batch_stride;
   const auto srsrc = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<uint8_t*>(src) + static_cast<int64_t>(lo_ok) * pitch, 0, max(hi_ok - lo_ok, 0) * pitch, 0x00020000);
   const auto drsrc = __builtin_amdgcn_make_buffer_rsrc(dst + static_cast<int64_t>(r0) * pitch, 0,
@@ -419,11 +462,21 @@ SwarGeom swar_geom(const SwarShape& sh, int ch, int steps, int64_t rows, int64_t
   return g;
 }
 
-// Launches the prefetch kernel can take: 4-byte lanes, whole dwords per row,
-// source and destination ranges under 2 GiB (32-bit buffer offsets).
+// Whole dwords per row of every image of a mixed-size launch (true without dims).
+bool pf_dims_ok(const StencilLaunch& a) {
+  if (a.dims_host)
+    for (int b = 0; b < a.batch; ++b)
+      if (a.dims_host[b].row_bytes % 4 != 0) return false;
+  return true;
+}
+
+// Launches the prefetch kernel can take: 4-byte lanes, whole dwords per row
+// (per image, when the launch carries dims), source and destination ranges
+// under 2 GiB (32-bit buffer offsets).
 bool pf_launch_ok(const StencilLaunch& a, int steps) {
   const int64_t src_rows = (a.r1 + steps) - (a.r0 - steps), dp = a.pitch;
-  return a.row_bytes % 4 == 0 && src_rows * a.pitch < (int64_t(1) << 31) && (a.r1 - a.r0) * dp < (int64_t(1) << 31);
+  return a.row_bytes % 4 == 0 && pf_dims_ok(a) && src_rows * a.pitch < (int64_t(1) << 31) &&
+         (a.r1 - a.r0) * dp < (int64_t(1) << 31);
 }
 
 // One launch of row I of the table: the tile kernel, or (PF) the buffer-op one.
@@ -443,7 +496,8 @@ void launch_tile(const StencilLaunch& a, hipStream_t s, int form) {
                                 static_cast<int>(a.r1), a.steps, static_cast<int>(a.g_row0), hmax,
                                 static_cast<int>(g.nstrips), static_cast<int>(g.pair_stride),
                                 static_cast<int>(g.row_tiles), xcd_swizzle_enabled() ? 1 : 0,
-                                static_cast<int>(g.tiles_per_image), a.batch > 1 ? a.batch_stride : int64_t(0));
+                                static_cast<int>(g.tiles_per_image), a.batch > 1 ? a.batch_stride : int64_t(0),
+                                a.dims);
   };
   if constexpr (PF)
     launch(swar_pf_kernel<CH, S.m, S.nw>(form, a.border), static_cast<int>(a.pitch));
@@ -636,15 +690,18 @@ void launch_choice(const StencilLaunch& a, Channels ch, hipStream_t stream, Swar
 
 // Empirical tuning: the model ranks the shapes, the best few are timed in both
 // step forms on the actual launch (fastest_candidate, tuning.hpp) and the
-// fastest (shape, form) is cached per (channels, steps, rows, row bytes, batch).
+// fastest (shape, form) is cached per (channels, steps, rows, row bytes, batch,
+// live workgroups of a mixed-size launch under the model's shape; 0: uniform).
 // Never while the stream is being captured into a graph (the engine tunes a
 // step's launches first).
 struct TuneKey {
   int ch, steps;
   int64_t rows, row_bytes;
   int batch;
+  int64_t live;
   bool operator<(const TuneKey& o) const {
-    return std::tie(ch, steps, rows, row_bytes, batch) < std::tie(o.ch, o.steps, o.rows, o.row_bytes, o.batch);
+    return std::tie(ch, steps, rows, row_bytes, batch, live) <
+           std::tie(o.ch, o.steps, o.rows, o.row_bytes, o.batch, o.live);
   }
 };
 std::mutex g_tune_mu;
@@ -659,6 +716,8 @@ SwarChoice tuned_choice(const StencilLaunch& a, Channels ch, hipStream_t stream,
   const auto runs = [&](const SwarShape& sh) { return swar_geom(sh, c, a.steps, rows, a.row_bytes).tiles > 0; };
   SwarChoice fallback;
   fallback.form = default_form();
+  PCONV_CHECK(pf_mode() != 1 || pf_dims_ok(a),
+              "swar prefetch kernel: needs whole dwords per row of every image of a dims launch");
   if (pf_mode() == 1 && pf_launch_ok(a, a.steps) && (override_shape(fallback.shape) || !shape_tuning_enabled())) {
     // forced prefetch kernel, untuned: the overridden shape if it has a
     // prefetch instantiation, else the first prefetch shape that runs
@@ -681,7 +740,15 @@ SwarChoice tuned_choice(const StencilLaunch& a, Channels ch, hipStream_t stream,
     if (!override_shape(fallback.shape)) fallback.shape = pick_swar_shape(a.steps, c, rows, a.row_bytes, a.batch);
     return fallback;
   }
-  const TuneKey key{c, a.steps, rows, a.row_bytes, a.batch};
+  // The model is asked with the envelope and the batch: a workgroup that
+  // leaves early in a smaller image is charged as a full one.
+  int64_t live = 0;
+  if (a.dims_host) {
+    const SwarGeom mg = swar_geom(pick_swar_shape(a.steps, c, rows, a.row_bytes, a.batch), c, a.steps, rows,
+                                  a.row_bytes, a.batch);
+    live = live_workgroups(a, mg.vbytes, mg.vrows, 2);
+  }
+  const TuneKey key{c, a.steps, rows, a.row_bytes, a.batch, live};
   {
     std::lock_guard<std::mutex> lk(g_tune_mu);
     auto it = g_tuned.find(key);
@@ -748,7 +815,7 @@ std::vector<std::pair<std::vector<int64_t>, SwarShape>> swar_tuned() {
   std::vector<std::pair<std::vector<int64_t>, SwarShape>> out;
   for (const auto& kv : g_tuned)
     out.push_back({{kv.first.ch, kv.first.steps, kv.first.rows, kv.first.row_bytes, kv.second.form,
-                    kv.second.kern, kv.first.batch},
+                    kv.second.kern, kv.first.batch, kv.first.live},
                    kv.second.shape});
   return out;
 }

@@ -61,6 +61,44 @@ inline void check_batch(const std::string& who, const StencilLaunch& a) {
                   std::to_string((a.frame_hi - a.frame_lo) * a.pitch) + " bytes): frames would overlap");
 }
 
+// Guards of a mixed-size batch (StencilLaunch::dims), shared by the launches
+// that take one: the table comes with its host copy, the launch covers whole
+// images, and every image is whole pixels inside the envelope.  `ch`: bytes
+// per pixel.  The kernels clamp the device entries to the envelope themselves,
+// so a device table that differs from the host copy still stays in the frame.
+inline void check_dims(const std::string& who, const StencilLaunch& a, int ch) {
+  PCONV_CHECK((a.dims == nullptr) == (a.dims_host == nullptr),
+              who + ": dims and dims_host must be given together (the device table and its host copy)");
+  if (!a.dims) return;
+  PCONV_CHECK(a.g_row0 == 0 && a.r0 == 0 && a.r1 == a.height,
+              who + ": dims needs whole images (g_row0 = 0, r0 = 0, r1 = height)");
+  for (int b = 0; b < a.batch; ++b) {
+    const ImageDims& d = a.dims_host[b];
+    PCONV_CHECK(d.row_bytes >= ch && d.row_bytes <= a.row_bytes && d.row_bytes % ch == 0,
+                who + ": dims[" + std::to_string(b) + "].row_bytes " + std::to_string(d.row_bytes) +
+                    " is no whole number of pixels inside the envelope's " + std::to_string(a.row_bytes));
+    PCONV_CHECK(d.height >= 1 && d.height <= a.height,
+                who + ": dims[" + std::to_string(b) + "].height " + std::to_string(d.height) +
+                    " is outside [1, the envelope's " + std::to_string(a.height) + "]");
+  }
+}
+
+// Workgroups of a mixed-size launch that have output in their image, for a
+// grid whose workgroup covers vbytes x vrows of output and packs `fold` column
+// strips (2: the SWAR strip pairs).  The tuners key on it (0: no dims), so a
+// uniform launch never shares a cache entry with a mixed one.
+inline int64_t live_workgroups(const StencilLaunch& a, int64_t vbytes, int64_t vrows, int fold) {
+  if (!a.dims_host || vbytes <= 0 || vrows <= 0) return 0;
+  int64_t live = 0;
+  for (int b = 0; b < a.batch; ++b) {
+    const int64_t strips = ceil_div<int64_t>(a.dims_host[b].row_bytes, vbytes);
+    // strip pair `col` holds strips col and col + pair_stride: it is live when its strip A is
+    const int64_t pair_stride = (ceil_div<int64_t>(a.row_bytes, vbytes) + fold - 1) / fold;
+    live += std::min(strips, pair_stride) * ceil_div<int64_t>(a.dims_host[b].height, vrows);
+  }
+  return live;
+}
+
 constexpr int kTuneRepeats = 3;
 constexpr int kTunePasses = 2;
 

@@ -55,6 +55,16 @@ BatchEngine::~BatchEngine() {
 void BatchEngine::check_n(const char* who, int n) const {
   PCONV_CHECK(n >= 0 && n <= capacity_, std::string(who) + ": " + std::to_string(n) + " images outside [0, capacity " +
                                             std::to_string(capacity_) + "]");
+  PCONV_CHECK(sizes_.empty() || n == static_cast<int>(sizes_.size()),
+              std::string(who) + ": " + std::to_string(n) + " images, but the mixed-size upload holds " +
+                  std::to_string(sizes_.size()));
+}
+
+// Mixed mode: the launch carries the extents table and its host copy.
+void BatchEngine::set_dims(StencilLaunch& a) const {
+  if (sizes_.empty()) return;
+  a.dims = reinterpret_cast<const ImageDims*>(dims_dev_.data());
+  a.dims_host = dims_host_.data();
 }
 
 // Copies: n pitched 2-D copies, one per image — the call every other engine of
@@ -63,6 +73,8 @@ void BatchEngine::check_n(const char* who, int n) const {
 // been timed against this form; tools/batch_sweep.py reports the end-to-end
 // time these copies give.
 void BatchEngine::upload(const uint8_t* p, int n, bool device) {
+  sizes_.clear();  // back to uniform launches
+  dims_host_.clear();
   check_n("BatchEngine::upload", n);
   PCONV_CHECK(p != nullptr || n == 0, "BatchEngine::upload: null source");
   const int64_t rb = lay_.row_bytes, img = geom_.bytes();
@@ -87,6 +99,61 @@ void BatchEngine::download(uint8_t* p, int n, bool device) {
     else
       PCONV_HIP_CHECK(hipMemcpy2DAsync(p + b * img, rb, s, lay_.pitch, rb, lay_.rows,
                                        device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, cs_));
+  }
+}
+
+void BatchEngine::upload_sized(const uint8_t* p, const std::vector<ImageSize>& sizes, bool device) {
+  std::vector<ImageDims> table = image_dims_table(geom_, capacity_, sizes);
+  PCONV_CHECK(p != nullptr || sizes.empty(), "BatchEngine::upload_sized: null source");
+  if (sizes.empty()) {
+    sizes_.clear();
+    dims_host_.clear();
+    return;
+  }
+  const size_t bytes = round_up<size_t>(sizeof(ImageDims) * static_cast<size_t>(capacity_), 16);
+  if (!dims_dev_.data()) {
+    dims_dev_ = DeviceBuffer(bytes);
+    dims_pin_ = PinnedBuffer(bytes);
+    std::memset(dims_pin_.data(), 0, bytes);
+    dims_ev_ = Event::create();
+  } else {
+    dims_ev_.sync();  // the previous copy out of the pinned words has completed
+  }
+  std::memcpy(dims_pin_.data(), table.data(), sizeof(ImageDims) * table.size());
+  if (opt_.kernel_copies)
+    launch_copy_rows(dims_pin_.data(), static_cast<int64_t>(bytes), dims_dev_.data(), static_cast<int64_t>(bytes),
+                     static_cast<int64_t>(bytes), 1, cs_);
+  else
+    PCONV_HIP_CHECK(hipMemcpyAsync(dims_dev_.data(), dims_pin_.data(), bytes, hipMemcpyHostToDevice, cs_));
+  dims_ev_.record(cs_);
+  // No frame is cleared: the kernels read nothing outside an image.
+  const uint8_t* s = p;
+  for (size_t b = 0; b < sizes.size(); ++b) {
+    const int64_t rb = table[b].row_bytes, rows = table[b].height;
+    uint8_t* d = frame_at(cur_) + static_cast<int64_t>(b) * stride_;
+    if (opt_.kernel_copies)
+      launch_copy_rows(s, rb, d, lay_.pitch, rb, rows, cs_);
+    else
+      PCONV_HIP_CHECK(hipMemcpy2DAsync(d, lay_.pitch, s, rb, rb, rows,
+                                       device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, cs_));
+    s += rb * rows;
+  }
+  sizes_ = sizes;
+  dims_host_ = std::move(table);
+}
+
+void BatchEngine::download_sized(uint8_t* p, bool device) {
+  PCONV_CHECK(p != nullptr || sizes_.empty(), "BatchEngine::download_sized: null destination");
+  uint8_t* d = p;
+  for (size_t b = 0; b < sizes_.size(); ++b) {
+    const int64_t rb = dims_host_[b].row_bytes, rows = dims_host_[b].height;
+    const uint8_t* s = frame_at(cur_) + static_cast<int64_t>(b) * stride_;  // the newest frames
+    if (opt_.kernel_copies)
+      launch_copy_rows(s, lay_.pitch, d, rb, rb, rows, cs_);
+    else
+      PCONV_HIP_CHECK(hipMemcpy2DAsync(d, rb, s, lay_.pitch, rb, rows,
+                                       device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, cs_));
+    d += rb * rows;
   }
 }
 
@@ -125,6 +192,7 @@ void BatchEngine::run(int reps, int n) {
         a.border = opt_.border;
         a.batch = n;
         a.batch_stride = stride_;
+        set_dims(a);
         launch_stencil(filter_, geom_.channels, a, cs_, opt_.variant);
         ++stats_.launches;
       }
@@ -153,6 +221,7 @@ void BatchEngine::launch_batch_residual(int n) {
   a.border = opt_.border;
   a.batch = n;
   a.batch_stride = stride_;
+  set_dims(a);
   launch_residual(filter_, geom_.channels, a, reinterpret_cast<uint64_t*>(res_count_.data()), cs_);
 }
 

@@ -5,6 +5,7 @@
 #include <cstdlib>
 #include <sstream>
 
+#include "pconv/batch_engine.hpp"
 #include "pconv/common.hpp"
 #include "pconv/filter.hpp"
 #include "pconv/image.hpp"
@@ -171,6 +172,32 @@ int reference_rows_division(int n_processes, int rows, int columns) {
     }
   }
   return best;
+}
+
+// ---------------------------------------------------------------- mixed-size batches
+// The host half of BatchEngine::upload_sized (batch_engine.hpp): no device call,
+// so the sanitized unit runner covers it.
+std::vector<ImageDims> image_dims_table(const ImageGeom& env, int capacity, const std::vector<ImageSize>& sizes) {
+  PCONV_CHECK(static_cast<int64_t>(sizes.size()) <= capacity,
+              "BatchEngine::upload_sized: " + std::to_string(sizes.size()) + " images exceed the capacity " +
+                  std::to_string(capacity));
+  std::vector<ImageDims> out;
+  out.reserve(sizes.size());
+  for (size_t b = 0; b < sizes.size(); ++b) {
+    const ImageSize& z = sizes[b];
+    PCONV_CHECK(z.width >= 1 && z.width <= env.width && z.height >= 1 && z.height <= env.height,
+                "BatchEngine::upload_sized: image " + std::to_string(b) + " (" + std::to_string(z.width) + "x" +
+                    std::to_string(z.height) + ") does not lie within the envelope " + std::to_string(env.width) +
+                    "x" + std::to_string(env.height));
+    out.push_back(ImageDims{static_cast<int32_t>(z.width * env.ch()), static_cast<int32_t>(z.height)});
+  }
+  return out;
+}
+
+int64_t packed_bytes(const ImageGeom& env, const std::vector<ImageSize>& sizes) {
+  int64_t total = 0;
+  for (const auto& z : sizes) total += z.width * env.ch() * z.height;
+  return total;
 }
 
 }  // namespace pconv

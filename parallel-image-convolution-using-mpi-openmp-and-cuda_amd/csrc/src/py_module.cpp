@@ -405,15 +405,30 @@ PYBIND11_MODULE(_pconv_native, m) {
                                {static_cast<py::ssize_t>(b.size())}, {1});
       });
 
+  // Mixed sizes (StencilLaunch::dims): `dims` is the host copy as a list of
+  // (row_bytes, height) pairs, `dims_ptr` the device table's address.
+  static const auto set_dims = [](StencilLaunch& a, std::vector<ImageDims>& host, const py::object& dims,
+                                  uintptr_t dims_ptr) {
+    if (!dims.is_none()) {
+      for (const auto& d : dims.cast<std::vector<std::pair<int32_t, int32_t>>>())
+        host.push_back(ImageDims{d.first, d.second});
+      PCONV_CHECK(static_cast<int64_t>(host.size()) == a.batch, "dims: the list must hold `batch` (row_bytes, height) pairs");
+      a.dims_host = host.data();
+    }
+    a.dims = reinterpret_cast<const ImageDims*>(dims_ptr);
+  };
   m.def(
       "launch_stencil",
       [](py::object filter, const std::string& ch, uintptr_t src, uintptr_t dst, int64_t pitch, int64_t row_bytes,
          int64_t r0, int64_t r1, int64_t frame_lo, int64_t frame_hi, int steps, int64_t g_row0, int64_t height,
-         uintptr_t stream, const std::string& variant, const std::string& border, int batch, int64_t batch_stride) {
+         uintptr_t stream, const std::string& variant, const std::string& border, int batch, int64_t batch_stride,
+         py::object dims, uintptr_t dims_ptr) {
         StencilLaunch a;
+        std::vector<ImageDims> dims_host;
         a.border = parse_border(border);
         a.batch = batch;
         a.batch_stride = batch_stride;
+        set_dims(a, dims_host, dims, dims_ptr);
         a.src = reinterpret_cast<const uint8_t*>(src);
         a.dst = reinterpret_cast<uint8_t*>(dst);
         a.pitch = pitch;
@@ -431,13 +446,16 @@ PYBIND11_MODULE(_pconv_native, m) {
       py::arg("filter"), py::arg("channels"), py::arg("src"), py::arg("dst"), py::arg("pitch"), py::arg("row_bytes"),
       py::arg("r0"), py::arg("r1"), py::arg("frame_lo"), py::arg("frame_hi"), py::arg("steps") = 1,
       py::arg("g_row0") = 0, py::arg("height") = (int64_t(1) << 40), py::arg("stream") = 0,
-      py::arg("variant") = "auto", py::arg("border") = "zero", py::arg("batch") = 1, py::arg("batch_stride") = 0);
+      py::arg("variant") = "auto", py::arg("border") = "zero", py::arg("batch") = 1, py::arg("batch_stride") = 0,
+      py::arg("dims") = py::none(), py::arg("dims_ptr") = 0);
   m.def(
       "launch_residual",
       [](py::object filter, const std::string& ch, uintptr_t src, int64_t pitch, int64_t row_bytes, int64_t r0,
          int64_t r1, int64_t frame_lo, int64_t frame_hi, int64_t g_row0, int64_t height, uintptr_t stream,
-         const std::string& border) {
+         const std::string& border, py::object dims, uintptr_t dims_ptr) {
         StencilLaunch a;
+        std::vector<ImageDims> dims_host;
+        set_dims(a, dims_host, dims, dims_ptr);
         a.border = parse_border(border);
         a.src = reinterpret_cast<const uint8_t*>(src);
         a.pitch = pitch;
@@ -463,17 +481,21 @@ PYBIND11_MODULE(_pconv_native, m) {
       py::arg("filter"), py::arg("channels"), py::arg("src"), py::arg("pitch"), py::arg("row_bytes"), py::arg("r0"),
       py::arg("r1"), py::arg("frame_lo"), py::arg("frame_hi"), py::arg("g_row0") = 0,
       py::arg("height") = (int64_t(1) << 40), py::arg("stream") = 0, py::arg("border") = "zero",
+      py::arg("dims") = py::none(), py::arg("dims_ptr") = 0,
       "Residual kernel on a frame (launch_stencil's geometry arguments): bytes of rows [r0, r1) that one more "
       "repetition would change; synchronises the stream.");
   m.def(
       "launch_residual_batch",
       [](py::object filter, const std::string& ch, uintptr_t src, int64_t pitch, int64_t row_bytes, int64_t r0,
          int64_t r1, int64_t frame_lo, int64_t frame_hi, uintptr_t counters, int batch, int64_t batch_stride,
-         int64_t g_row0, int64_t height, uintptr_t stream, const std::string& border) {
+         int64_t g_row0, int64_t height, uintptr_t stream, const std::string& border, py::object dims,
+         uintptr_t dims_ptr) {
         StencilLaunch a;
+        std::vector<ImageDims> dims_host;
         a.border = parse_border(border);
         a.batch = batch;
         a.batch_stride = batch_stride;
+        set_dims(a, dims_host, dims, dims_ptr);
         a.src = reinterpret_cast<const uint8_t*>(src);
         a.pitch = pitch;
         a.row_bytes = row_bytes;
@@ -493,7 +515,7 @@ PYBIND11_MODULE(_pconv_native, m) {
       py::arg("filter"), py::arg("channels"), py::arg("src"), py::arg("pitch"), py::arg("row_bytes"), py::arg("r0"),
       py::arg("r1"), py::arg("frame_lo"), py::arg("frame_hi"), py::arg("counters"), py::arg("batch"),
       py::arg("batch_stride"), py::arg("g_row0") = 0, py::arg("height") = (int64_t(1) << 40), py::arg("stream") = 0,
-      py::arg("border") = "zero",
+      py::arg("border") = "zero", py::arg("dims") = py::none(), py::arg("dims_ptr") = 0,
       "Residual kernel on `batch` frames batch_stride bytes apart in one launch: image b's count is ADDED to "
       "counters[b] (a device pointer to at least `batch` uint64 of the caller's, neither zeroed nor read here); "
       "synchronises the stream.");
@@ -773,6 +795,11 @@ PYBIND11_MODULE(_pconv_native, m) {
 
   // Up to `capacity` whole images of one geometry, one fused launch per
   // `fuse` repetitions for all of them (batch_engine.hpp).
+  static const auto to_sizes = [](const std::vector<std::pair<int64_t, int64_t>>& sizes) {
+    std::vector<ImageSize> out;
+    for (const auto& z : sizes) out.push_back(ImageSize{z.first, z.second});
+    return out;
+  };
   py::class_<BatchEngine>(m, "BatchEngine")
       .def(py::init([](int64_t w, int64_t h, const std::string& ch, int capacity, py::object filter, int device,
                        int fuse, const std::string& variant, const std::string& border) {
@@ -821,6 +848,42 @@ PYBIND11_MODULE(_pconv_native, m) {
           "download_ptr",
           [](BatchEngine& e, uintptr_t ptr, int n, bool device) { e.download(reinterpret_cast<uint8_t*>(ptr), n, device); },
           py::arg("ptr"), py::arg("n"), py::arg("device") = false)
+      .def(
+          "upload_sized",
+          [](BatchEngine& e, py::buffer host, const std::vector<std::pair<int64_t, int64_t>>& sizes) {
+            const HostView v = host_view(host, false);
+            const std::vector<ImageSize> sz = to_sizes(sizes);
+            (void)image_dims_table(e.geom(), e.capacity(), sz);  // the sizes are checked before the buffer's
+            PCONV_CHECK(v.size >= packed_bytes(e.geom(), sz), "host buffer too small");
+            e.upload_sized(v.ptr, sz);
+          },
+          py::arg("host"), py::arg("sizes"),
+          "mixed sizes: `host` holds the images of `sizes` [(width, height)] back to back with tight rows, each "
+          "within the engine's width x height (the envelope); lasts until the next plain upload")
+      .def(
+          "upload_sized_ptr",
+          [](BatchEngine& e, uintptr_t ptr, const std::vector<std::pair<int64_t, int64_t>>& sizes, bool device) {
+            e.upload_sized(reinterpret_cast<const uint8_t*>(ptr), to_sizes(sizes), device);
+          },
+          py::arg("ptr"), py::arg("sizes"), py::arg("device") = false)
+      .def(
+          "download_sized",
+          [](BatchEngine& e, py::buffer host) {
+            const HostView v = host_view(host, true);
+            PCONV_CHECK(v.size >= packed_bytes(e.geom(), e.sizes()), "host buffer too small");
+            e.download_sized(v.ptr);
+          },
+          py::arg("host"))
+      .def(
+          "download_sized_ptr",
+          [](BatchEngine& e, uintptr_t ptr, bool device) { e.download_sized(reinterpret_cast<uint8_t*>(ptr), device); },
+          py::arg("ptr"), py::arg("device") = false)
+      .def_property_readonly("sizes",
+                             [](const BatchEngine& e) {
+                               std::vector<std::pair<int64_t, int64_t>> out;
+                               for (const auto& z : e.sizes()) out.emplace_back(z.width, z.height);
+                               return out;
+                             })
       .def("wait_stream", [](BatchEngine& e, uintptr_t s) { e.wait_stream(reinterpret_cast<hipStream_t>(s)); })
       .def("signal_stream", [](BatchEngine& e, uintptr_t s) { e.signal_stream(reinterpret_cast<hipStream_t>(s)); })
       .def("run", &BatchEngine::run, py::arg("reps"), py::arg("n"), py::call_guard<py::gil_scoped_release>())

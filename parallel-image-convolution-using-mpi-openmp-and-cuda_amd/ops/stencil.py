@@ -334,6 +334,12 @@ class BatchEngine:
     ``run_numpy`` / ``run_tensor`` / ``__call__`` take a stack of
     ``n <= capacity`` images, ``(n, H, W)`` or ``(n, H, W, C)``, and return the
     same container type; a CUDA tensor never leaves the device.
+
+    Mixed sizes: ``run_images`` / ``residual_images`` /
+    ``run_images_until_stable`` take a sequence of ``n <= capacity`` images of
+    ANY sizes within ``width`` x ``height`` (the engine's geometry is then an
+    envelope).  Each is convolved as a lone image of its own size, in the same
+    ``ceil(reps / fuse)`` launches; the results come back as a list.
     """
 
     def __init__(self, width: int, height: int, channels: str = "grey", capacity: int = 1, filter="gaussian",
@@ -442,6 +448,87 @@ class BatchEngine:
             raise ValueError("check_every must be >= 1")
         out, st = self._with_frames(stack, lambda n: self._eng.run_until_stable(int(max_reps), k, n))
         return out, [StableInfo(int(s[0]), bool(s[1]), int(s[2]), int(s[3])) for s in (st or [])]
+
+
+    # ---- mixed sizes ---------------------------------------------------
+    def _check_images(self, images):
+        """The images as a list, their (width, height) list and whether they
+        are tensors (all of one kind, checked by the caller for the API)."""
+        seq = list(images)
+        if len(seq) > self.capacity:
+            raise ValueError(f"{len(seq)} images exceed the engine's capacity {self.capacity}")
+        sizes = []
+        for im in seq:
+            w, h, ch = image_geometry(tuple(im.shape))
+            if ch != self.channels or not (1 <= w <= self.width and 1 <= h <= self.height):
+                raise ValueError(f"image of shape {tuple(im.shape)} does not lie within the engine's "
+                                 f"{self.width}x{self.height} {self.channels} envelope")
+            sizes.append((w, h))
+        return seq, sizes
+
+    def _with_images(self, images, work):
+        """Upload the images top-left into their frames, ``work(n)`` on them,
+        download each image's region: ``([out], work's result)``."""
+        seq, sizes = self._check_images(images)
+        n = self._n = len(seq)
+        if n == 0:
+            return [], None
+        tensors = [isinstance(im, torch.Tensor) for im in seq]
+        if all(tensors) and all(im.device.type == "cuda" for im in seq):
+            flat = torch.cat([im.contiguous().reshape(-1) for im in seq])
+            out = torch.empty_like(flat)
+            ts = torch.cuda.current_stream(flat.device).cuda_stream
+            self._eng.wait_stream(ts)
+            self._eng.upload_sized_ptr(flat.data_ptr(), sizes, device=True)
+            res = work(n)
+            self._eng.download_sized_ptr(out.data_ptr(), device=True)
+            self._eng.signal_stream(ts)
+            flat.record_stream(torch.cuda.current_stream(flat.device))
+            wrap = lambda a: a  # noqa: E731
+        else:
+            arrs = [np.ascontiguousarray(im.cpu().numpy() if t else im, dtype=np.uint8) for im, t in zip(seq, tensors)]
+            flat = np.concatenate([a.reshape(-1) for a in arrs])
+            out = np.empty_like(flat)
+            self._eng.upload_sized(flat, sizes)
+            res = work(n)
+            self._eng.download_sized(out)
+            self._eng.synchronize()
+            wrap = None
+        outs, at = [], 0
+        for im, t in zip(seq, tensors):
+            k = int(np.prod(tuple(im.shape)))
+            piece = out[at:at + k].reshape(tuple(im.shape))
+            at += k
+            if wrap is None:
+                piece = torch.from_numpy(piece.copy()) if t else piece.copy()
+            outs.append(piece)
+        return outs, res
+
+    def run_images(self, images, reps: int) -> list:
+        """``reps`` repetitions of every image of the sequence, each as a lone
+        image of its own size; a list in input order, in the input's container
+        type (CUDA tensors stay on the device)."""
+        return self._with_images(images, lambda n: self._eng.run(int(reps), n))[0]
+
+    def residual_images(self, images=None) -> np.ndarray:
+        """:meth:`residual` for mixed sizes: of ``images``, or (``None``) of the
+        frames the engine holds after its last mixed-size call."""
+        if images is None:
+            res = self._eng.residual(self._n) if self._n else []
+        else:
+            res = self._with_images(images, self._eng.residual)[1] or []
+        return np.asarray(res, dtype=np.int64).reshape(-1)
+
+    def run_images_until_stable(self, images, max_reps: int, check_every: Optional[int] = None):
+        """:meth:`run_until_stable` for mixed sizes: ``([out], [StableInfo])``,
+        entry b what a single-image run of image b returns."""
+        if max_reps < 0:
+            raise ValueError("max_reps must be >= 0")
+        k = _GPU_CHECK_LAUNCHES * self.fuse if check_every is None else int(check_every)
+        if k < 1:
+            raise ValueError("check_every must be >= 1")
+        outs, st = self._with_images(images, lambda n: self._eng.run_until_stable(int(max_reps), k, n))
+        return outs, [StableInfo(int(s[0]), bool(s[1]), int(s[2]), int(s[3])) for s in (st or [])]
 
 
 # convolve_batch's own engine cache (the single-image engines keep theirs).
@@ -631,6 +718,188 @@ def residual_batch(images, filter="gaussian", backend: str = "auto", device: Opt
                            for i in range(n_img)], dtype=np.int64)
     eng, cap = _hip_batch_engine(stack, is_tensor, geo, flt, device, None, "auto", border, None)
     return np.concatenate([eng.residual(stack[i:i + cap]) for i in range(0, n_img, cap)])
+
+
+# ---- images of different sizes ------------------------------------------------
+
+_CH_COUNT = {"grey": 1, "rgb": 3, "rgba": 4}
+
+
+def size_buckets(sizes, channels, fuse, min_fill: float = 0.5, batch_size: Optional[int] = None,
+                 max_bytes: int = _BATCH_BYTES):
+    """Group images of different sizes into envelopes for :class:`BatchEngine`.
+
+    ``sizes``: ``[(width, height)]``; ``channels``: ``"grey" | "rgb" | "rgba"``
+    or the count; ``fuse``: the ghost rows of a frame, an int or a callable
+    ``(width, height) -> int`` asked with a bucket's envelope.  Returns
+    ``[((W, H), [indices])]``: every index once, ``(W, H)`` the members' maximum
+    width and maximum height.
+
+    Pure Python and deterministic: the indices are sorted by (height, width)
+    descending (stable) and buckets are filled greedily — an image joins the
+    open bucket while its fill ``sum(w_i * h_i) / (n * W * H)`` stays
+    ``>= min_fill``, ``n <= batch_size`` and the engine's two allocations,
+    ``2 * n * frame bytes of the envelope``, stay within ``max_bytes``; a
+    bucket always takes at least one image.
+
+    ``min_fill = 0.5`` is a waste policy (at most half of a bucket's tile work
+    and frame memory goes to area outside its images), like the 1 GiB of
+    ``max_bytes``: neither is a tuned number.
+    """
+    ch = _CHANNELS[channels] if channels in _CHANNELS else channels
+    if ch not in _CH_COUNT:
+        raise ValueError(f"unknown channels {channels!r}")
+    if not 0.0 <= float(min_fill) <= 1.0:
+        raise ValueError("min_fill must lie in [0, 1]")
+    if batch_size is not None and int(batch_size) < 1:
+        raise ValueError("batch_size must be >= 1")
+    sizes = [(int(w), int(h)) for w, h in sizes]
+    if any(w < 1 or h < 1 for w, h in sizes):
+        raise ValueError("image sizes must be >= 1x1")
+    fuse_of = fuse if callable(fuse) else (lambda w, h: int(fuse))
+    order = sorted(range(len(sizes)), key=lambda i: (-sizes[i][1], -sizes[i][0]))
+    buckets = []
+    members, env, area = [], (0, 0), 0
+    for i in order:
+        w, h = sizes[i]
+        if members:
+            n = len(members) + 1
+            e = (max(env[0], w), max(env[1], h))
+            fits = ((area + w * h) >= float(min_fill) * n * e[0] * e[1]
+                    and (batch_size is None or n <= int(batch_size))
+                    and 2 * n * _frame_bytes(e[0], e[1], ch, fuse_of(*e)) <= max_bytes)
+            if fits:
+                members.append(i)
+                env, area = e, area + w * h
+                continue
+            buckets.append((env, members))
+        members, env, area = [i], (w, h), w * h
+    if members:
+        buckets.append((env, members))
+    return buckets
+
+
+def _prepare_many(images, filter, backend, border, batch_size, min_fill):
+    """The argument checks the mixed-size entry points share: (filter, images
+    as a list, is_tensor, channels name, resolved backend)."""
+    if batch_size is not None and int(batch_size) < 1:
+        raise ValueError("batch_size must be >= 1")
+    if not 0.0 <= float(min_fill) <= 1.0:
+        raise ValueError("min_fill must lie in [0, 1]")
+    flt = get_filter(filter)
+    check_border(border)
+    if isinstance(images, (np.ndarray, torch.Tensor)):
+        raise TypeError("images must be a sequence of images (a stack of same-size images goes to convolve_batch)")
+    seq = list(images)
+    if backend not in ("auto", "hip", "omp", "cpu", "numpy"):
+        raise ValueError(f"unknown backend {backend!r} (hip|omp|cpu|numpy|auto)")
+    if not seq:
+        return flt, seq, False, None, backend
+    kinds = {isinstance(im, torch.Tensor) for im in seq}
+    if len(kinds) != 1 or not all(isinstance(im, (torch.Tensor, np.ndarray)) for im in seq):
+        raise TypeError("images must be all NumPy arrays or all torch tensors")
+    is_tensor = kinds.pop()
+    if any(im.dtype != (torch.uint8 if is_tensor else np.uint8) for im in seq):
+        raise TypeError("image tensor must be uint8" if is_tensor else "image array must be uint8")
+    chans = {image_geometry(tuple(im.shape))[2] for im in seq}
+    if len(chans) != 1:
+        raise ValueError(f"images must share one channel count, got {sorted(chans)}")
+    if any(int(s) < 1 for im in seq for s in im.shape):
+        raise ValueError("images must be at least 1x1")
+    if is_tensor and len({im.device for im in seq}) != 1:
+        raise ValueError("image tensors must share one device")
+    if backend == "auto":
+        backend = "hip" if (is_tensor and seq[0].is_cuda) else _default_backend()
+    return flt, seq, is_tensor, chans.pop(), backend
+
+
+def _hip_buckets(seq, is_tensor, ch, flt, device, fuse, variant, border, batch_size, min_fill):
+    """(cached BatchEngine, indices) per size bucket of the images."""
+    n = require_native()
+    if device is None:
+        device = seq[0].device.index if (is_tensor and seq[0].is_cuda) else 0
+    device = int(device or 0)
+    c = _CH_COUNT[ch]
+    nf = flt.to_native()
+    fuse_of = (lambda w, h: int(n.auto_fuse(nf, variant, w * h * c, c))) if fuse is None else (lambda w, h: int(fuse))
+    sizes = [image_geometry(tuple(im.shape))[:2] for im in seq]
+    for (w, h), idx in size_buckets(sizes, ch, fuse_of, min_fill, batch_size):
+        yield _cached_batch_engine(w, h, ch, len(idx), flt, device, fuse_of(w, h), variant, border), idx
+
+
+def convolve_many(images, reps: int = 1, filter="gaussian", backend: str = "auto", device: Optional[int] = None,
+                  fuse: Optional[int] = None, variant: str = "auto", threads: int = 0, border: str = "zero",
+                  batch_size: Optional[int] = None, min_fill: float = 0.5) -> list:
+    """``convolve`` for a sequence of 8-bit images of ANY sizes.
+
+    ``images``: uint8 ``(H, W)`` / ``(H, W, C)`` arrays or tensors that share
+    one channel count and one container kind (tensors one device).  Entry i of
+    the returned list equals ``convolve(images[i], reps, ...)``, in the input's
+    container and on its device; ``[]`` gives ``[]``.
+
+    On the ``hip`` backend the images are grouped by :func:`size_buckets`
+    (``min_fill``, ``batch_size``, 1 GiB of frames) and every bucket advances
+    in the fused launches of one cached :class:`BatchEngine` whose geometry is
+    the bucket's envelope: ``ceil(reps / fuse)`` launches per bucket whatever
+    its images' number and sizes.  The other backends loop over the images.
+    """
+    if reps < 0:
+        raise ValueError("reps must be >= 0")
+    flt, seq, is_tensor, ch, backend = _prepare_many(images, filter, backend, border, batch_size, min_fill)
+    if not seq:
+        return []
+    if backend != "hip":
+        return [convolve(im, reps, flt, backend=backend, threads=threads, border=border) for im in seq]
+    outs = [None] * len(seq)
+    for eng, idx in _hip_buckets(seq, is_tensor, ch, flt, device, fuse, variant, border, batch_size, min_fill):
+        for i, o in zip(idx, eng.run_images([seq[i] for i in idx], reps)):
+            outs[i] = o
+    return outs
+
+
+def convolve_many_until_stable(images, max_reps: int, filter="gaussian", check_every: Optional[int] = None,
+                               backend: str = "auto", device: Optional[int] = None, fuse: Optional[int] = None,
+                               variant: str = "auto", threads: int = 0, border: str = "zero",
+                               batch_size: Optional[int] = None, min_fill: float = 0.5):
+    """``convolve_until_stable`` for a sequence of images of any sizes
+    (:func:`convolve_many`'s inputs and buckets).  Returns ``([out],
+    [StableInfo])``: entry i of both is what ``convolve_until_stable(images[i],
+    max_reps, filter, check_every, ...)`` returns.  On the ``hip`` backend every
+    check counts a bucket's images in one launch of the residual kernel."""
+    if max_reps < 0:
+        raise ValueError("max_reps must be >= 0")
+    if check_every is not None and int(check_every) < 1:
+        raise ValueError("check_every must be >= 1")
+    flt, seq, is_tensor, ch, backend = _prepare_many(images, filter, backend, border, batch_size, min_fill)
+    if not seq:
+        return [], []
+    if backend != "hip":
+        res = [convolve_until_stable(im, max_reps, flt, check_every=check_every, backend=backend, threads=threads,
+                                     border=border) for im in seq]
+        return [r[0] for r in res], [r[1] for r in res]
+    outs, infos = [None] * len(seq), [None] * len(seq)
+    for eng, idx in _hip_buckets(seq, is_tensor, ch, flt, device, fuse, variant, border, batch_size, min_fill):
+        got, st = eng.run_images_until_stable([seq[i] for i in idx], int(max_reps), check_every)
+        for i, o, info in zip(idx, got, st):
+            outs[i], infos[i] = o, info
+    return outs, infos
+
+
+def residual_many(images, filter="gaussian", backend: str = "auto", device: Optional[int] = None, threads: int = 0,
+                  border: str = "zero", batch_size: Optional[int] = None, min_fill: float = 0.5) -> np.ndarray:
+    """:func:`residual` of a sequence of images of any sizes, ``(N,)`` int64:
+    equals ``[residual(img, ...) for img in images]``; on the ``hip`` backend
+    one launch of the residual kernel per size bucket."""
+    flt, seq, is_tensor, ch, backend = _prepare_many(images, filter, backend, border, batch_size, min_fill)
+    if not seq:
+        return np.zeros((0,), dtype=np.int64)
+    if backend != "hip":
+        return np.asarray([residual(im, flt, backend=backend, threads=threads, border=border) for im in seq],
+                          dtype=np.int64)
+    out = np.zeros((len(seq),), dtype=np.int64)
+    for eng, idx in _hip_buckets(seq, is_tensor, ch, flt, device, None, "auto", border, batch_size, min_fill):
+        out[idx] = eng.residual_images([seq[i] for i in idx])
+    return out
 
 
 def convolve_file(path: str, width: int, height: int, reps: int, channels: str = "grey", filter="gaussian",

@@ -60,10 +60,10 @@ def shapes_of(n, ch, rows, row_bytes, batch, steps, model_args):
     (SWAR kernels) or, untuned, the model's pick."""
     if model_args is None:
         return []  # float kernel: its tuned table is not exported
-    got = [list(k) + list(s) for k, s in n.swar_tuned()
+    got = [(list(k), list(s)) for k, s in n.swar_tuned()
            if k[0] == ch and k[2] == rows and k[3] == row_bytes and k[6] == batch]
     if got:
-        return [{"steps": g[1], "form": g[4], "kernel": "bufop" if g[5] else "tile", "shape": g[7:]} for g in got]
+        return [{"steps": k[1], "form": k[4], "kernel": "bufop" if k[5] else "tile", "shape": s} for k, s in got]
     pick, _ = n.swar_model(steps, *model_args, batch=batch)
     return [{"steps": steps, "model_pick": list(pick)}]
 
