@@ -14,7 +14,19 @@
 // run_until_stable advances all n images in chunks with such a check after
 // each and reports for every image what a single-image run of it would have
 // reported.  Converged images keep advancing with the rest (they rewrite the
-// same bytes) until the last image converges or max_reps is reached.
+// same bytes) until the last image converges or max_reps is reached — unless
+// the caller asks for compaction.
+//
+// Compaction (run_until_stable's `compact`, off by default): an image found
+// fixed at check j is retired — from check j + 1 and chunk j + 2 on, the fused
+// and the residual launches carry a table of the open images only
+// (StencilLaunch::active) and their grids shrink to those images.  The chunk
+// in flight while check j was read still holds the image, which is what makes
+// both of its ping-pong frames equal (see run_until_stable in the .cpp), so
+// results, downloads and later runs are those of compact = false, byte for
+// byte.  RunStats::image_launches shows the work that was retired.  A
+// compacted launch never starts first-use tuning: it runs the tuned entry of
+// its own image count if one exists, else the latency model's tile.
 //
 // Mixed sizes: the engine's geometry is then an ENVELOPE.  upload_sized puts
 // images of any sizes within it top-left into their frames and hands every
@@ -24,9 +36,10 @@
 // an image, so a larger image's stale bytes never leak.  The mode lasts until
 // the next plain upload().
 //
-// Out of scope here (see docs/ARCHITECTURE.md §5): hipGraph capture, retiring
-// converged images from the launches (compaction), more than one GPU; and for
-// mixed sizes the CLI, the service and the pipelines.
+// Out of scope here (see docs/ARCHITECTURE.md §5): hipGraph capture, more than
+// one GPU, a device-side rebuild of the active-image table (it would remove
+// the one-chunk lag of compaction); and for mixed sizes and compaction the
+// CLI, the service and the pipelines.
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -108,7 +121,10 @@ class BatchEngine {
   // their last count.  The frames hold max(reps made) repetitions, which for a
   // converged image are its fixed point's bytes.  last_stats() afterwards
   // carries the summed launches and the host-timed loop.
-  std::vector<StableStats> run_until_stable(int max_reps, int check_every, int n);
+  //   compact: images found fixed are retired from the launches that follow
+  // (the header comment); the returned entries and the frames' image bytes are
+  // exactly those of compact = false, last_stats().image_launches is smaller.
+  std::vector<StableStats> run_until_stable(int max_reps, int check_every, int n, bool compact = false);
   // Diagnostics: ms of each of `launches` residual launches over images [0, n)
   // of the current frames (stream events around the launch alone).
   std::vector<double> time_residual(int launches, int n);
@@ -121,6 +137,8 @@ class BatchEngine {
  private:
   void check_n(const char* who, int n) const;
   void set_dims(StencilLaunch& a) const;
+  void set_active(StencilLaunch& a) const;
+  void upload_active(const std::vector<int32_t>& table);
   void launch_batch_residual(int n);
   void enqueue_residual(int n);
   std::vector<uint64_t> finish_residual(int n);
@@ -145,6 +163,15 @@ class BatchEngine {
   PinnedBuffer dims_pin_;
   DeviceBuffer dims_dev_;
   Event dims_ev_;
+  // Compaction: the open images of the run_until_stable in progress, in
+  // increasing order (empty: every launch covers images [0, n)) — the host
+  // copy the guards read —, the pinned words the table is copied out of, the
+  // device table of `capacity` entries (allocated on first use), and the event
+  // behind the latest copy.
+  std::vector<int32_t> active_host_;
+  PinnedBuffer active_pin_;
+  DeviceBuffer active_dev_;
+  Event active_ev_;
   Stream own_cs_;
   hipStream_t cs_ = nullptr;
   Event ev_t0_, ev_t1_, ev_sync_;

@@ -129,6 +129,9 @@ struct RunStats {
   double wall_ms = 0;      // host wall time of the enqueue+sync
   int launches = 0;
   int exchanges = 0;
+  // BatchEngine: over all fused launches of the run, the sum of the number of
+  // images in each launch's grid (launches x n unless images were retired).
+  int64_t image_launches = 0;
 };
 
 class BandEngine {

@@ -71,6 +71,23 @@ struct StencilLaunch {
   // (g_row0 = 0, r0 = 0, r1 = height); batch = 1 is allowed.
   const ImageDims* dims = nullptr;
   const ImageDims* dims_host = nullptr;
+  // Active images (temporal kernels and the residual kernel): a launch over
+  // SOME of the `batch_frames` frames that lie batch_stride apart.  `batch` is
+  // then the number of table entries and the grid is that many images wide;
+  // entry k is the frame index of the grid's k-th image, whose frame lies
+  // active[k] * batch_stride after frame 0 (in src and dst alike; the residual
+  // kernel adds to counter[active[k]]).  Frames the table does not name are
+  // neither read nor written, and their counters are not touched.  The entries
+  // are strictly increasing inside [0, batch_frames).  `active` is device
+  // memory (the kernels clamp each entry to batch_frames - 1), `active_host`
+  // the host copy the guards read; both or neither.  `dims` stays indexed by
+  // FRAME: with a table it has batch_frames entries.  Null: image k is frame k
+  // and batch_frames is ignored.  A launch with a table runs its model's tile
+  // (or the tuned entry of its own key, if one exists) and never starts
+  // first-use tuning.
+  const int32_t* active = nullptr;
+  const int32_t* active_host = nullptr;
+  int batch_frames = 1;
 };
 
 enum class KernelVariant : int {
@@ -117,6 +134,9 @@ void prepare_float_temporal(const Filter& f, Channels ch, const StencilLaunch& a
 // to counter[b], all in the one launch; no counter beyond a.batch is touched.
 // The batch guards are launch_stencil's (check_batch), every geometry guard
 // holds per image, and batch x workgroups per image must stay below 2^31.
+// With an active-image table (a.active) `counter` points at a.batch_frames
+// counters, the grid's k-th image adds to counter[active[k]], and the counters
+// of frames the table does not name are not touched.
 void launch_residual(const Filter& f, Channels ch, const StencilLaunch& a, uint64_t* counter, hipStream_t stream);
 // Rows one workgroup of the residual kernel covers (tests place image heights around it).
 constexpr int kResidualBlockRows = 32;

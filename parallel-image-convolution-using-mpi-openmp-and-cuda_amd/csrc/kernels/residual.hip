@@ -106,12 +106,17 @@ __global__ __launch_bounds__(256) void k_residual(const uint8_t* __restrict__ sr
                                                   int r0, int r1, Taps9 tp, int img_lo, int img_hi, int blocks_x,
                                                   int blocks_per_image, int64_t batch_stride,
                                                   unsigned long long* __restrict__ counter,
-                                                  const ImageDims* __restrict__ dims) {
+                                                  const ImageDims* __restrict__ dims,
+                                                  const int32_t* __restrict__ active, unsigned last_frame) {
   __shared__ u32 part[4];
   // Image of the batch: from the workgroup id (scalar); it only moves the
-  // frame pointer and picks the counter.
-  const unsigned img = blockIdx.x / static_cast<unsigned>(blocks_per_image);
+  // frame pointer and picks the counter.  Active images: the grid's slot names
+  // its frame through the table (one scalar load; the unsigned min keeps a
+  // wrong table inside the batch_frames frames and counters); from there on
+  // img is a frame index.
+  unsigned img = blockIdx.x / static_cast<unsigned>(blocks_per_image);
   const unsigned blk = blockIdx.x - img * static_cast<unsigned>(blocks_per_image);
+  if (active != nullptr) img = min(static_cast<unsigned>(active[img]), last_frame);
   src += static_cast<int64_t>(img) * batch_stride;
   const int bx = static_cast<int>(blk % static_cast<unsigned>(blocks_x));
   const int by = static_cast<int>(blk / static_cast<unsigned>(blocks_x));
@@ -173,12 +178,13 @@ void launch_ch(const Filter& f, const StencilLaunch& a, uint64_t* counter, hipSt
   auto* ctr = reinterpret_cast<unsigned long long*>(counter);
   const int rb = static_cast<int>(a.row_bytes), r0 = static_cast<int>(a.r0), r1 = static_cast<int>(a.r1);
   const int nbx = static_cast<int>(bx), per_image = static_cast<int>(bx * by), img_lo = lo, img_hi = hi;
-  const int64_t stride = a.batch > 1 ? a.batch_stride : int64_t(0);
+  const int64_t stride = a.batch > 1 || a.active ? a.batch_stride : int64_t(0);
+  const unsigned last_frame = a.active ? static_cast<unsigned>(a.batch_frames - 1) : 0u;
   with_bool(!int_form_allowed(f), [&](auto fl) {
     with_bool(a.border == Border::Replicate, [&](auto rep) {
       k_residual<CH, decltype(fl)::value, decltype(rep)::value>
           <<<grid, block, 0, s>>>(a.src, a.pitch, rb, r0, r1, tp, img_lo, img_hi, nbx, per_image, stride, ctr,
-                                  a.dims);
+                                  a.dims, a.active, last_frame);
     });
   });
 }
@@ -187,6 +193,7 @@ void launch_ch(const Filter& f, const StencilLaunch& a, uint64_t* counter, hipSt
 
 void launch_residual(const Filter& f, Channels ch, const StencilLaunch& a_in, uint64_t* counter, hipStream_t stream) {
   StencilLaunch a = a_in;
+  check_active("launch_residual", a);  // before anything reads the table's entries
   check_dims("launch_residual", a, channel_count(ch));  // on the rows as given: whole images
   // rows outside the global image are no part of the map (launch_stencil's clip)
   a.r0 = std::max(a.r0, -a.g_row0);

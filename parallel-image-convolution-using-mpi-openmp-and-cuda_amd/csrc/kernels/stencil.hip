@@ -246,12 +246,14 @@ namespace {
 // non-zero border runs on the temporal kernels for every step count (an
 // int_exact filter is bit-identical in the float kernel by definition), and
 // so does an image batch: only the temporal kernels' grids carry one; and so
-// does a launch with per-image extents (dims), which only they read.
+// does a launch with per-image extents (dims) or an active-image table
+// (active), which only they read.
 bool resolve_launch(const Filter& f, StencilLaunch& a, KernelVariant& v) {
   a.r0 = std::max(a.r0, -a.g_row0);
   a.r1 = std::min(a.r1, a.height - a.g_row0);
   if (a.r1 <= a.r0) return false;
-  const bool fused = a.steps > 1 || a.border != Border::Zero || a.batch > 1 || a.dims || a.dims_host;
+  const bool fused = a.steps > 1 || a.border != Border::Zero || a.batch > 1 || a.dims || a.dims_host || a.active ||
+                     a.active_host;
   if (v == KernelVariant::Auto)
     v = f.binomial121 ? (fused ? KernelVariant::Temporal : KernelVariant::Binomial)
                       : (fused ? KernelVariant::FloatTemporal
@@ -266,6 +268,7 @@ bool resolve_launch(const Filter& f, StencilLaunch& a, KernelVariant& v) {
 void prepare_stencil(const Filter& f, Channels ch, const StencilLaunch& a_in, hipStream_t stream, KernelVariant v) {
   StencilLaunch a = a_in;
   if (!resolve_launch(f, a, v) || a.steps > kMaxFusedSteps) return;
+  if (a.active || a.active_host) return;  // an active-image launch never tunes: nothing to settle
   if (v == KernelVariant::Temporal && f.binomial121) prepare_swar(a, ch, stream);
   if (v == KernelVariant::FloatTemporal) prepare_float_temporal(f, ch, a, stream);
 }
@@ -279,6 +282,10 @@ void launch_stencil(const Filter& f, Channels ch, const StencilLaunch& a_in, hip
   PCONV_CHECK(a.row_bytes < (int64_t(1) << 31) && a.r1 - a.frame_lo < (int64_t(1) << 31),
               "launch_stencil: geometry exceeds 32-bit kernel indices");
   check_batch("launch_stencil", a);
+  PCONV_CHECK((!a.active && !a.active_host) || v == KernelVariant::Temporal || v == KernelVariant::FloatTemporal,
+              "launch_stencil: active not supported by kernel '" + std::string(kernel_variant_name(v)) +
+                  "' (temporal and float_temporal only)");
+  check_active("launch_stencil", a);  // before anything reads the table's entries
   PCONV_CHECK((!a.dims && !a.dims_host) || v == KernelVariant::Temporal || v == KernelVariant::FloatTemporal,
               "launch_stencil: dims not supported by kernel '" + std::string(kernel_variant_name(v)) +
                   "' (temporal and float_temporal only)");

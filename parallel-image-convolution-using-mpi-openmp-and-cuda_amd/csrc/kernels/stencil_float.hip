@@ -267,20 +267,26 @@ template <int CH, bool UNIFORM, int M, int NW, bool REP = false>
 __global__ __launch_bounds__(64 * NW) void k_float_temporal(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
                                                             int64_t pitch, int row_bytes, int r0, int r1, int steps,
                                                             int g_row0, int height, FloatTaps tp,
-                                                            int64_t batch_stride, const ImageDims* __restrict__ dims) {
+                                                            int64_t batch_stride, const ImageDims* __restrict__ dims,
+                                                            const int32_t* __restrict__ active, unsigned last_frame) {
   __shared__ uint2 lds[2][NW][2][64];  // [parity][wave][top/bottom][lane]
   // Image of the batch: grid.z (scalar); it only moves the two base pointers.
+  // Active images: grid.z is a slot and names its frame through the table (one
+  // scalar load); the unsigned min keeps a wrong table inside the allocation's
+  // batch_frames frames.  From here on img is a frame index.
   // The empty asm settles both sums here, in scalar registers: from this line
   // on the kernel holds what the single-image kernel held (two pointers), and
   // the compiler allocates the registers of everything below as it did then.
-  src += static_cast<int64_t>(blockIdx.z) * batch_stride;
-  dst += static_cast<int64_t>(blockIdx.z) * batch_stride;
+  unsigned img = blockIdx.z;
+  if (active != nullptr) img = min(static_cast<unsigned>(active[img]), last_frame);
+  src += static_cast<int64_t>(img) * batch_stride;
+  dst += static_cast<int64_t>(img) * batch_stride;
   asm volatile("" : "+s"(src), "+s"(dst));
   // Mixed sizes: the image's own extent replaces the envelope's (one scalar
-  // load; blockIdx.z is workgroup-uniform).  The min keeps a wrong table inside
+  // load; img is workgroup-uniform).  The min keeps a wrong table inside
   // the frame.  Everything below reads the two values as it reads the arguments.
   if (dims != nullptr) {
-    const ImageDims d = dims[blockIdx.z];
+    const ImageDims d = dims[img];
     row_bytes = min(d.row_bytes, row_bytes);
     height = min(d.height, height);
     // A tile of the envelope's grid with no output in this image: gone before
@@ -516,7 +522,8 @@ void launch_ft_shape(const StencilLaunch& a, const FloatTaps& tp, hipStream_t s)
   kern<<<grid, dim3(64 * NW), 0, s>>>(
       a.src, a.dst, a.pitch, static_cast<int>(a.row_bytes), static_cast<int>(a.r0), static_cast<int>(a.r1), a.steps,
       static_cast<int>(a.g_row0), static_cast<int>(std::min<int64_t>(a.height, int64_t(1) << 30)), tp,
-      a.batch > 1 ? a.batch_stride : int64_t(0), a.dims);
+      a.batch > 1 || a.active ? a.batch_stride : int64_t(0), a.dims, a.active,
+      a.active ? static_cast<unsigned>(a.batch_frames - 1) : 0u);
 }
 
 template <int CH, bool UNIFORM>
@@ -566,7 +573,8 @@ FloatShape tuned_ft_shape(const StencilLaunch& a, const FloatTaps& tp, hipStream
     auto it = g_ft_tuned.find(key);
     if (it != g_ft_tuned.end()) return it->second;
   }
-  if (stream_capturing(s)) return model;
+  // (an active-image launch never tunes: its own cached entry above, else the model; stencil_swar.hip)
+  if (stream_capturing(s) || a.active) return model;
   std::vector<FloatShape> ok;
   for (const auto& c : kFtShapes)
     if (ft_geom(c, CH, a.steps, rows, a.row_bytes).ok) ok.push_back(c);
@@ -589,6 +597,7 @@ void float_temporal(const Filter& f, Channels ch, const StencilLaunch& a, hipStr
   PCONV_CHECK(a.height < (int64_t(1) << 30) && a.g_row0 < (int64_t(1) << 30), "float temporal kernel: rows exceed 2^30");
   PCONV_CHECK(a.row_bytes > 0 && a.row_bytes < (int64_t(1) << 30), "float temporal kernel: row bytes out of range");
   check_batch("launch_float_temporal", a);
+  check_active("launch_float_temporal", a);
   check_dims("launch_float_temporal", a, channel_count(ch));
   PCONV_CHECK(a.batch <= 65535, "launch_float_temporal: batch " + std::to_string(a.batch) + " exceeds grid.z (65535)");
   FloatTaps tp;

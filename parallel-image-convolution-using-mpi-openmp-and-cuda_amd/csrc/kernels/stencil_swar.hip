@@ -131,7 +131,8 @@ __global__ __launch_bounds__(64 * NW) void k_swar(const uint8_t* __restrict__ sr
                                                   int64_t pitch, int row_bytes, int r0, int r1,
                                                   int steps, int g_row0, int height, int nstrips, int pair_stride,
                                                   int row_tiles, int xcd_swizzle, int tiles_per_image,
-                                                  int64_t batch_stride, const ImageDims* __restrict__ dims) {
+                                                  int64_t batch_stride, const ImageDims* __restrict__ dims,
+                                                  const int32_t* __restrict__ active, unsigned last_frame) {
   constexpr int NP = LW;       // pairs per row per lane
   constexpr int NQ = NP / 4;   // uint4 per row per lane
   using CT = typename Chunk<NP>::T;
@@ -156,8 +157,13 @@ __global__ __launch_bounds__(64 * NW) void k_swar(const uint8_t* __restrict__ sr
     tile = xcd * q + min(xcd, rem) + local;
   }
   {
-    const int img = tile / tiles_per_image;
+    int img = tile / tiles_per_image;
     tile -= img * tiles_per_image;
+    // Active images: the grid's slot names its frame through the table (one
+    // scalar load; the slot is workgroup-uniform).  The unsigned min keeps a
+    // wrong table inside the allocation's batch_frames frames.  From here on
+    // img is a frame index, as without a table.
+    if (active != nullptr) img = static_cast<int>(min(static_cast<unsigned>(active[img]), last_frame));
     src += static_cast<int64_t>(img) * batch_stride;
     dst += static_cast<int64_t>(img) * batch_stride;
     // Mixed sizes: the image's own extent replaces the envelope's (one scalar
@@ -262,7 +268,8 @@ __global__ __launch_bounds__(64 * NW) void k_swar_pf(const uint8_t* __restrict__
                                                      int pitch, int row_bytes, int r0, int r1,
                                                      int steps, int g_row0, int height, int nstrips, int pair_stride,
                                                      int row_tiles, int xcd_swizzle, int tiles_per_image,
-                                                     int64_t batch_stride, const ImageDims* __restrict__ dims) {
+                                                     int64_t batch_stride, const ImageDims* __restrict__ dims,
+                                                     const int32_t* __restrict__ active, unsigned last_frame) {
   constexpr int LW = 4, NP = 4, NQ = 1;
   constexpr u32 kOut = 0x80000000u;  // offset past every descriptor's range
   __shared__ uint4 lds[2][NW][2][NQ][64];
@@ -281,8 +288,11 @@ __global__ __launch_bounds__(64 * NW) void k_swar_pf(const uint8_t* __restrict__
     const int q = nwg >> 3, rem = nwg & 7, xcd = tile & 7, local = tile >> 3;
     tile = xcd * q + min(xcd, rem) + local;
   }
-  const int img = tile / tiles_per_image;
+  int img = tile / tiles_per_image;
   tile -= img * tiles_per_image;
+  // Active images (as k_swar): the slot names its frame through the table; the
+  // unsigned min keeps a wrong table inside the batch_frames frames.
+  if (active != nullptr) img = static_cast<int>(min(static_cast<unsigned>(active[img]), last_frame));
   // Mixed sizes: the image's own extent replaces the envelope's (one scalar
   // load; img is workgroup-uniform; whole dwords per row are the launch's
   // contract per image).  The min keeps a wrong table inside the frame.
@@ -462,11 +472,12 @@ SwarGeom swar_geom(const SwarShape& sh, int ch, int steps, int64_t rows, int64_t
   return g;
 }
 
-// Whole dwords per row of every image of a mixed-size launch (true without dims).
+// Whole dwords per row of every image of a mixed-size launch (true without
+// dims); with an active-image table, of the frames it names.
 bool pf_dims_ok(const StencilLaunch& a) {
   if (a.dims_host)
     for (int b = 0; b < a.batch; ++b)
-      if (a.dims_host[b].row_bytes % 4 != 0) return false;
+      if (a.dims_host[frame_of(a, b)].row_bytes % 4 != 0) return false;
   return true;
 }
 
@@ -496,8 +507,9 @@ void launch_tile(const StencilLaunch& a, hipStream_t s, int form) {
                                 static_cast<int>(a.r1), a.steps, static_cast<int>(a.g_row0), hmax,
                                 static_cast<int>(g.nstrips), static_cast<int>(g.pair_stride),
                                 static_cast<int>(g.row_tiles), xcd_swizzle_enabled() ? 1 : 0,
-                                static_cast<int>(g.tiles_per_image), a.batch > 1 ? a.batch_stride : int64_t(0),
-                                a.dims);
+                                static_cast<int>(g.tiles_per_image),
+                                a.batch > 1 || a.active ? a.batch_stride : int64_t(0), a.dims, a.active,
+                                a.active ? static_cast<unsigned>(a.batch_frames - 1) : 0u);
   };
   if constexpr (PF)
     launch(swar_pf_kernel<CH, S.m, S.nw>(form, a.border), static_cast<int>(a.pitch));
@@ -759,7 +771,11 @@ SwarChoice tuned_choice(const StencilLaunch& a, Channels ch, hipStream_t stream,
     }
   }
   fallback.shape = pick_swar_shape(a.steps, c, rows, a.row_bytes, a.batch);
-  if (!may_measure || stream_capturing(stream)) return fallback;
+  // A launch with an active-image table never tunes: the live counts of a
+  // compacting loop are arbitrary, and a dozen timed candidates per count
+  // would cost more than the retired images save.  It ran the cached entry of
+  // its own key above if there was one; else the model's pick for its grid.
+  if (!may_measure || stream_capturing(stream) || a.active) return fallback;
   std::vector<std::pair<double, SwarShape>> ranked;
   for (const auto& t : kTiles) {
     const double cost = swar_launch_cycles(t.shape, a.steps, c, rows, a.row_bytes, a.batch);

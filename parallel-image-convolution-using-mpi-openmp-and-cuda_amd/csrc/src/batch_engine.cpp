@@ -67,6 +67,47 @@ void BatchEngine::set_dims(StencilLaunch& a) const {
   a.dims_host = dims_host_.data();
 }
 
+// Compaction: the launch covers the open images only.  `batch` becomes the
+// number of table entries, the frames (and the extents table) stay the call's.
+void BatchEngine::set_active(StencilLaunch& a) const {
+  if (active_host_.empty()) return;
+  a.batch_frames = a.batch;
+  a.batch = static_cast<int>(active_host_.size());
+  a.active = reinterpret_cast<const int32_t*>(active_dev_.data());
+  a.active_host = active_host_.data();
+}
+
+// The table of open images goes to the device as the extents table does: out
+// of pinned words that are rewritten only after the event behind the previous
+// copy out of them, and copied ON THE COMPUTE STREAM.  One device region is
+// enough: the stream is in order, so the copy lands after every launch that
+// was enqueued with the previous table has finished, and before every launch
+// enqueued after it starts.
+void BatchEngine::upload_active(const std::vector<int32_t>& table) {
+  PCONV_CHECK(!table.empty() && static_cast<int>(table.size()) <= capacity_,
+              "BatchEngine: an active-image table must hold 1 to `capacity` entries");
+  const size_t bytes = round_up<size_t>(sizeof(int32_t) * static_cast<size_t>(capacity_), 16);
+  if (!active_dev_.data()) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    PCONV_CHECK(hipStreamIsCapturing(cs_, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone,
+                "BatchEngine: the active-image table cannot be allocated on a capturing stream");
+    active_dev_ = DeviceBuffer(bytes);
+    active_pin_ = PinnedBuffer(bytes);
+    std::memset(active_pin_.data(), 0, bytes);
+    active_ev_ = Event::create();
+  } else {
+    active_ev_.sync();  // the previous copy out of the pinned words has completed
+  }
+  std::memcpy(active_pin_.data(), table.data(), sizeof(int32_t) * table.size());
+  if (opt_.kernel_copies)
+    launch_copy_rows(active_pin_.data(), static_cast<int64_t>(bytes), active_dev_.data(), static_cast<int64_t>(bytes),
+                     static_cast<int64_t>(bytes), 1, cs_);
+  else
+    PCONV_HIP_CHECK(hipMemcpyAsync(active_dev_.data(), active_pin_.data(), bytes, hipMemcpyHostToDevice, cs_));
+  active_ev_.record(cs_);
+  active_host_ = table;
+}
+
 // Copies: n pitched 2-D copies, one per image — the call every other engine of
 // this library uses for its rows.  One hipMemcpy3DAsync could describe the
 // whole batch (the frames sit a whole number of pitches apart), but it has not
@@ -193,8 +234,10 @@ void BatchEngine::run(int reps, int n) {
         a.batch = n;
         a.batch_stride = stride_;
         set_dims(a);
+        set_active(a);
         launch_stencil(filter_, geom_.channels, a, cs_, opt_.variant);
         ++stats_.launches;
+        stats_.image_launches += a.batch;
       }
       cur_ ^= 1;
     }
@@ -222,6 +265,7 @@ void BatchEngine::launch_batch_residual(int n) {
   a.batch = n;
   a.batch_stride = stride_;
   set_dims(a);
+  set_active(a);
   launch_residual(filter_, geom_.channels, a, reinterpret_cast<uint64_t*>(res_count_.data()), cs_);
 }
 
@@ -292,7 +336,20 @@ std::vector<double> BatchEngine::time_residual(int launches, int n) {
   return ms;
 }
 
-std::vector<StableStats> BatchEngine::run_until_stable(int max_reps, int check_every, int n) {
+// Compaction (`compact`): an image whose count was zero at check j leaves the
+// launches.  The chunk after that check is already in flight with it, so the
+// first launches without it are check j + 1 and chunk j + 2.
+//   Why no frame parity is kept per image: a retired image X satisfies
+// step(X) = X in the frame check j read, and it takes part in at least one
+// fused launch AFTER that check — the chunk in flight — which writes
+// step^t(X) = X into the other ping-pong frame.  Both frames of a retired
+// image therefore hold the same image bytes, whichever of them cur_ names when
+// the loop ends: download / download_sized go on reading cur_ for every image,
+// and a later plain run(reps, n) continues every image correctly.  The "at
+// least one launch" is checked below for every image at the moment it is
+// retired, and nothing is retired when the loop ends at the check (no chunk
+// follows it).
+std::vector<StableStats> BatchEngine::run_until_stable(int max_reps, int check_every, int n, bool compact) {
   PCONV_CHECK(max_reps >= 0, "repetitions must be >= 0");
   PCONV_CHECK(check_every >= 1, "check_every must be >= 1");
   check_n("BatchEngine::run_until_stable", n);
@@ -301,24 +358,44 @@ std::vector<StableStats> BatchEngine::run_until_stable(int max_reps, int check_e
     stats_ = RunStats{};
     return st;
   }
+  // The table lives for this call only, also when a launch throws.
+  struct ClearActive {
+    std::vector<int32_t>& t;
+    ~ClearActive() { t.clear(); }
+  } clear_active{active_host_};
+  active_host_.clear();
   RunStats sum;
   const double w0 = wall_seconds();
+  // Fused launches image b has taken part in, and that number when the latest
+  // check was enqueued (the invariant above).
+  std::vector<int64_t> launched(static_cast<size_t>(n), 0), at_check(static_cast<size_t>(n), 0);
   auto chunk = [&](int k) {
     run(k, n);
     sum.launches += stats_.launches;
+    sum.image_launches += stats_.image_launches;
+    if (active_host_.empty())
+      for (auto& l : launched) l += stats_.launches;
+    else
+      for (const int32_t b : active_host_) launched[b] += stats_.launches;
+  };
+  auto check = [&] {
+    at_check = launched;
+    enqueue_residual(n);
   };
   int done = std::min(check_every, max_reps);
   int checks = 0, open = n;
   chunk(done);
-  enqueue_residual(n);
+  check();
   for (;;) {
     // The next chunk is enqueued BEFORE the host waits for this check's
     // counts, so the GPU never idles over the read-back.  If every count turns
     // out zero, the chunk in flight repeats the fixed points' bytes.
     const int next = std::min(check_every, max_reps - done);
     if (next > 0) chunk(next);
+    // (a retired image's counter no longer moves: its difference reads zero)
     const std::vector<uint64_t> cnt = finish_residual(n);
     ++checks;
+    bool retire = false;
     for (int b = 0; b < n; ++b) {
       StableStats& s = st[b];
       if (s.converged) {
@@ -330,11 +407,30 @@ std::vector<StableStats> BatchEngine::run_until_stable(int max_reps, int check_e
       s.checks = checks;
       s.reps_done = done;
       s.converged = cnt[b] == 0;
-      if (s.converged) --open;
+      if (s.converged) {
+        --open;
+        retire = true;
+      }
     }
     if (open == 0 || next == 0) break;
+    if (compact && retire) {
+      // The images this check found fixed leave the launches from here on:
+      // the next check and the chunk after the one in flight.
+      std::vector<int32_t> table;
+      for (int b = 0; b < n; ++b) {
+        if (!st[b].converged) {
+          table.push_back(b);
+          continue;
+        }
+        if (st[b].checks != checks) continue;  // retired at an earlier check
+        PCONV_CHECK(launched[b] > at_check[b],
+                    "BatchEngine::run_until_stable: image " + std::to_string(b) +
+                        " would be retired without a fused launch since its zero check (its two frames could differ)");
+      }
+      upload_active(table);
+    }
     done += next;
-    enqueue_residual(n);
+    check();
   }
   synchronize();
   sum.wall_ms = (wall_seconds() - w0) * 1e3;

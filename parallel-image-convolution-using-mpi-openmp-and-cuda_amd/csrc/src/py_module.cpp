@@ -407,27 +407,49 @@ PYBIND11_MODULE(_pconv_native, m) {
 
   // Mixed sizes (StencilLaunch::dims): `dims` is the host copy as a list of
   // (row_bytes, height) pairs, `dims_ptr` the device table's address.
+  // With an active-image table (set_active first) the list is indexed by frame
+  // and holds `batch_frames` pairs.
   static const auto set_dims = [](StencilLaunch& a, std::vector<ImageDims>& host, const py::object& dims,
                                   uintptr_t dims_ptr) {
     if (!dims.is_none()) {
       for (const auto& d : dims.cast<std::vector<std::pair<int32_t, int32_t>>>())
         host.push_back(ImageDims{d.first, d.second});
-      PCONV_CHECK(static_cast<int64_t>(host.size()) == a.batch, "dims: the list must hold `batch` (row_bytes, height) pairs");
+      if (a.active_host)
+        PCONV_CHECK(static_cast<int64_t>(host.size()) == a.batch_frames,
+                    "dims: with an active table the list must hold `batch_frames` (row_bytes, height) pairs");
+      else
+        PCONV_CHECK(static_cast<int64_t>(host.size()) == a.batch,
+                    "dims: the list must hold `batch` (row_bytes, height) pairs");
       a.dims_host = host.data();
     }
     a.dims = reinterpret_cast<const ImageDims*>(dims_ptr);
+  };
+  // Active images (StencilLaunch::active): `active` is the host copy as a list
+  // of frame indices (`batch` of them), `active_ptr` the device table's
+  // address, `batch_frames` the number of frames at the stride.
+  static const auto set_active = [](StencilLaunch& a, std::vector<int32_t>& host, const py::object& active,
+                                    uintptr_t active_ptr, int batch_frames) {
+    if (!active.is_none()) {
+      host = active.cast<std::vector<int32_t>>();
+      PCONV_CHECK(static_cast<int64_t>(host.size()) == a.batch, "active: the list must hold `batch` frame indices");
+      a.active_host = host.data();
+    }
+    a.active = reinterpret_cast<const int32_t*>(active_ptr);
+    a.batch_frames = batch_frames;
   };
   m.def(
       "launch_stencil",
       [](py::object filter, const std::string& ch, uintptr_t src, uintptr_t dst, int64_t pitch, int64_t row_bytes,
          int64_t r0, int64_t r1, int64_t frame_lo, int64_t frame_hi, int steps, int64_t g_row0, int64_t height,
          uintptr_t stream, const std::string& variant, const std::string& border, int batch, int64_t batch_stride,
-         py::object dims, uintptr_t dims_ptr) {
+         py::object dims, uintptr_t dims_ptr, py::object active, uintptr_t active_ptr, int batch_frames) {
         StencilLaunch a;
         std::vector<ImageDims> dims_host;
+        std::vector<int32_t> active_host;
         a.border = parse_border(border);
         a.batch = batch;
         a.batch_stride = batch_stride;
+        set_active(a, active_host, active, active_ptr, batch_frames);
         set_dims(a, dims_host, dims, dims_ptr);
         a.src = reinterpret_cast<const uint8_t*>(src);
         a.dst = reinterpret_cast<uint8_t*>(dst);
@@ -447,7 +469,8 @@ PYBIND11_MODULE(_pconv_native, m) {
       py::arg("r0"), py::arg("r1"), py::arg("frame_lo"), py::arg("frame_hi"), py::arg("steps") = 1,
       py::arg("g_row0") = 0, py::arg("height") = (int64_t(1) << 40), py::arg("stream") = 0,
       py::arg("variant") = "auto", py::arg("border") = "zero", py::arg("batch") = 1, py::arg("batch_stride") = 0,
-      py::arg("dims") = py::none(), py::arg("dims_ptr") = 0);
+      py::arg("dims") = py::none(), py::arg("dims_ptr") = 0, py::arg("active") = py::none(),
+      py::arg("active_ptr") = 0, py::arg("batch_frames") = 1);
   m.def(
       "launch_residual",
       [](py::object filter, const std::string& ch, uintptr_t src, int64_t pitch, int64_t row_bytes, int64_t r0,
@@ -489,12 +512,14 @@ PYBIND11_MODULE(_pconv_native, m) {
       [](py::object filter, const std::string& ch, uintptr_t src, int64_t pitch, int64_t row_bytes, int64_t r0,
          int64_t r1, int64_t frame_lo, int64_t frame_hi, uintptr_t counters, int batch, int64_t batch_stride,
          int64_t g_row0, int64_t height, uintptr_t stream, const std::string& border, py::object dims,
-         uintptr_t dims_ptr) {
+         uintptr_t dims_ptr, py::object active, uintptr_t active_ptr, int batch_frames) {
         StencilLaunch a;
         std::vector<ImageDims> dims_host;
+        std::vector<int32_t> active_host;
         a.border = parse_border(border);
         a.batch = batch;
         a.batch_stride = batch_stride;
+        set_active(a, active_host, active, active_ptr, batch_frames);
         set_dims(a, dims_host, dims, dims_ptr);
         a.src = reinterpret_cast<const uint8_t*>(src);
         a.pitch = pitch;
@@ -516,9 +541,11 @@ PYBIND11_MODULE(_pconv_native, m) {
       py::arg("r1"), py::arg("frame_lo"), py::arg("frame_hi"), py::arg("counters"), py::arg("batch"),
       py::arg("batch_stride"), py::arg("g_row0") = 0, py::arg("height") = (int64_t(1) << 40), py::arg("stream") = 0,
       py::arg("border") = "zero", py::arg("dims") = py::none(), py::arg("dims_ptr") = 0,
+      py::arg("active") = py::none(), py::arg("active_ptr") = 0, py::arg("batch_frames") = 1,
       "Residual kernel on `batch` frames batch_stride bytes apart in one launch: image b's count is ADDED to "
       "counters[b] (a device pointer to at least `batch` uint64 of the caller's, neither zeroed nor read here); "
-      "synchronises the stream.");
+      "with an active table, on the `batch` frames it names out of `batch_frames`, each adding to its frame's "
+      "counter; synchronises the stream.");
   m.attr("RESIDUAL_BLOCK_ROWS") = kResidualBlockRows;
   m.def("set_swar_shape", &set_swar_shape, py::arg("lw") = 0, py::arg("m") = 0, py::arg("nw") = 0,
         "Force the SWAR temporal tile shape (lw=0: back to the latency model).");
@@ -597,7 +624,8 @@ PYBIND11_MODULE(_pconv_native, m) {
       .def_readonly("loop_ms", &RunStats::loop_ms)
       .def_readonly("wall_ms", &RunStats::wall_ms)
       .def_readonly("launches", &RunStats::launches)
-      .def_readonly("exchanges", &RunStats::exchanges);
+      .def_readonly("exchanges", &RunStats::exchanges)
+      .def_readonly("image_launches", &RunStats::image_launches);
 
   py::class_<HaloTransport, PyHaloTransport, std::shared_ptr<HaloTransport>>(m, "HaloTransport")
       .def(py::init<>())
@@ -892,18 +920,19 @@ PYBIND11_MODULE(_pconv_native, m) {
            "per-image bytes of the newest frames of images [0, n) that one more repetition would change (one launch)")
       .def(
           "run_until_stable",
-          [](BatchEngine& e, int max_reps, int check_every, int n) {
+          [](BatchEngine& e, int max_reps, int check_every, int n, bool compact) {
             std::vector<StableStats> st;
             {
               py::gil_scoped_release nogil;
-              st = e.run_until_stable(max_reps, check_every, n);
+              st = e.run_until_stable(max_reps, check_every, n, compact);
             }
             py::list out;
             for (const auto& s : st) out.append(py::make_tuple(s.reps_done, s.converged, s.residual, s.checks));
             return out;
           },
-          py::arg("max_reps"), py::arg("check_every"), py::arg("n"),
-          "[(reps_done, converged, residual, checks)] of images [0, n), each as a single-image run would report it")
+          py::arg("max_reps"), py::arg("check_every"), py::arg("n"), py::arg("compact") = false,
+          "[(reps_done, converged, residual, checks)] of images [0, n), each as a single-image run would report it; "
+          "compact: converged images are retired from the launches that follow (same results, fewer image_launches)")
       .def("time_residual", &BatchEngine::time_residual, py::arg("launches"), py::arg("n"),
            py::call_guard<py::gil_scoped_release>(),
            "diagnostics: ms of each of `launches` residual launches over images [0, n) (stream events)")

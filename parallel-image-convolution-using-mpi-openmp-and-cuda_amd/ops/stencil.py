@@ -434,19 +434,24 @@ class BatchEngine:
             res = self._with_frames(stack, self._eng.residual)[1] or []
         return np.asarray(res, dtype=np.int64).reshape(-1)
 
-    def run_until_stable(self, stack, max_reps: int, check_every: Optional[int] = None):
+    def run_until_stable(self, stack, max_reps: int, check_every: Optional[int] = None, compact: bool = False):
         """All images of ``stack`` in chunks of ``check_every`` repetitions
         (default 16 x fuse) with a per-image residual check after each, until
         every image is at its fixed point or at ``max_reps``.  Returns ``(out,
         [StableInfo] * n)``: ``out[b]`` and entry b are what a single-image run
         of image b returns (an image that converged at an earlier check than
-        the rest went on rewriting the same bytes)."""
+        the rest went on rewriting the same bytes).
+
+        ``compact``: an image found fixed at a check is retired from the
+        launches that follow the chunk already in flight; the return values are
+        identical, ``stats.image_launches`` shows the work saved.  Retired
+        launches run the latency model's tile (no first-use tuning)."""
         if max_reps < 0:
             raise ValueError("max_reps must be >= 0")
         k = _GPU_CHECK_LAUNCHES * self.fuse if check_every is None else int(check_every)
         if k < 1:
             raise ValueError("check_every must be >= 1")
-        out, st = self._with_frames(stack, lambda n: self._eng.run_until_stable(int(max_reps), k, n))
+        out, st = self._with_frames(stack, lambda n: self._eng.run_until_stable(int(max_reps), k, n, bool(compact)))
         return out, [StableInfo(int(s[0]), bool(s[1]), int(s[2]), int(s[3])) for s in (st or [])]
 
 
@@ -519,15 +524,17 @@ class BatchEngine:
             res = self._with_images(images, self._eng.residual)[1] or []
         return np.asarray(res, dtype=np.int64).reshape(-1)
 
-    def run_images_until_stable(self, images, max_reps: int, check_every: Optional[int] = None):
+    def run_images_until_stable(self, images, max_reps: int, check_every: Optional[int] = None,
+                                compact: bool = False):
         """:meth:`run_until_stable` for mixed sizes: ``([out], [StableInfo])``,
-        entry b what a single-image run of image b returns."""
+        entry b what a single-image run of image b returns (``compact`` as
+        there: same return values, converged images leave the launches)."""
         if max_reps < 0:
             raise ValueError("max_reps must be >= 0")
         k = _GPU_CHECK_LAUNCHES * self.fuse if check_every is None else int(check_every)
         if k < 1:
             raise ValueError("check_every must be >= 1")
-        outs, st = self._with_images(images, lambda n: self._eng.run_until_stable(int(max_reps), k, n))
+        outs, st = self._with_images(images, lambda n: self._eng.run_until_stable(int(max_reps), k, n, bool(compact)))
         return outs, [StableInfo(int(s[0]), bool(s[1]), int(s[2]), int(s[3])) for s in (st or [])]
 
 
@@ -668,7 +675,7 @@ def convolve_batch(images, reps: int = 1, filter="gaussian", backend: str = "aut
 def convolve_batch_until_stable(images, max_reps: int, filter="gaussian", check_every: Optional[int] = None,
                                 backend: str = "auto", device: Optional[int] = None, fuse: Optional[int] = None,
                                 variant: str = "auto", threads: int = 0, border: str = "zero",
-                                batch_size: Optional[int] = None):
+                                batch_size: Optional[int] = None, compact: bool = False):
     """``convolve_until_stable`` for N same-size 8-bit images at once.
 
     Inputs, backends, the engine cache and ``batch_size`` are
@@ -680,6 +687,12 @@ def convolve_batch_until_stable(images, max_reps: int, filter="gaussian", check_
     chunk's loop ends when its last image has converged (the others rewrite
     their fixed point's bytes meanwhile) or at ``max_reps``.  The other
     backends loop over the images.
+
+    ``compact`` (``hip`` backend): images found fixed are retired from the
+    launches after the chunk in flight (:meth:`BatchEngine.run_until_stable`).
+    The ``cpu`` and ``numpy`` backends accept and ignore it: they loop per
+    image and already stop each image at its own fixed point.  The return
+    values are identical for both settings on every backend.
     """
     if max_reps < 0:
         raise ValueError("max_reps must be >= 0")
@@ -698,8 +711,9 @@ def convolve_batch_until_stable(images, max_reps: int, filter="gaussian", check_
 
     eng, cap = _hip_batch_engine(stack, is_tensor, geo, flt, device, fuse, variant, border, batch_size)
     if n_img <= cap:
-        return eng.run_until_stable(stack, int(max_reps), check_every)
-    res = [eng.run_until_stable(stack[i:i + cap], int(max_reps), check_every) for i in range(0, n_img, cap)]
+        return eng.run_until_stable(stack, int(max_reps), check_every, compact)
+    res = [eng.run_until_stable(stack[i:i + cap], int(max_reps), check_every, compact)
+           for i in range(0, n_img, cap)]
     outs = [r[0] for r in res]
     return (torch.cat(outs) if is_tensor else np.concatenate(outs)), [info for r in res for info in r[1]]
 
@@ -860,12 +874,15 @@ def convolve_many(images, reps: int = 1, filter="gaussian", backend: str = "auto
 def convolve_many_until_stable(images, max_reps: int, filter="gaussian", check_every: Optional[int] = None,
                                backend: str = "auto", device: Optional[int] = None, fuse: Optional[int] = None,
                                variant: str = "auto", threads: int = 0, border: str = "zero",
-                               batch_size: Optional[int] = None, min_fill: float = 0.5):
+                               batch_size: Optional[int] = None, min_fill: float = 0.5, compact: bool = False):
     """``convolve_until_stable`` for a sequence of images of any sizes
     (:func:`convolve_many`'s inputs and buckets).  Returns ``([out],
     [StableInfo])``: entry i of both is what ``convolve_until_stable(images[i],
     max_reps, filter, check_every, ...)`` returns.  On the ``hip`` backend every
-    check counts a bucket's images in one launch of the residual kernel."""
+    check counts a bucket's images in one launch of the residual kernel.
+    ``compact`` is :func:`convolve_batch_until_stable`'s, per bucket: same
+    return values; the ``cpu`` and ``numpy`` backends accept and ignore it
+    (they already stop each image at its own fixed point)."""
     if max_reps < 0:
         raise ValueError("max_reps must be >= 0")
     if check_every is not None and int(check_every) < 1:
@@ -879,7 +896,7 @@ def convolve_many_until_stable(images, max_reps: int, filter="gaussian", check_e
         return [r[0] for r in res], [r[1] for r in res]
     outs, infos = [None] * len(seq), [None] * len(seq)
     for eng, idx in _hip_buckets(seq, is_tensor, ch, flt, device, fuse, variant, border, batch_size, min_fill):
-        got, st = eng.run_images_until_stable([seq[i] for i in idx], int(max_reps), check_every)
+        got, st = eng.run_images_until_stable([seq[i] for i in idx], int(max_reps), check_every, compact)
         for i, o, info in zip(idx, got, st):
             outs[i], infos[i] = o, info
     return outs, infos

@@ -3,7 +3,7 @@
 one launch against image by image, and of the batch loop that uses it:
 
     tools/batch_converge_cost.py W H {grey,rgb,rgba} N [--border B] [--filter F] [--check-every K]
-                                 [--max-reps R] [--iters I]
+                                 [--max-reps R] [--iters I] [--compact]
 
 Image k is the synthetic random image of seed k with its values shifted right
 by 0, 2, 4 or 6 bits (k mod 4): contrasts differ, so the images reach their
@@ -19,7 +19,12 @@ Prints one JSON line:
   * `run_until_stable(max_reps, K, N)` against `run(max_reps, N)`, both timed
     on the host from the enqueue to the end of the stream, uploads excluded;
   * the per-image `reps_done`, `converged` flags and the number of checks.
-Every list holds all `--iters` samples; the summary fields are medians."""
+Every list holds all `--iters` samples; the summary fields are medians.
+
+With `--compact` a second JSON line follows: `run_until_stable(max_reps, K, N)`
+with compaction off and on, alternated in this process (one untimed pass of
+each first), both loops as all samples and as min / median / max, the launches
+and `image_launches` of both, and the tuned tile table."""
 import argparse
 import json
 import os
@@ -44,6 +49,8 @@ def main():
     p.add_argument("--check-every", type=int, default=None)
     p.add_argument("--max-reps", type=int, default=512)
     p.add_argument("--iters", type=int, default=7)
+    p.add_argument("--compact", action="store_true",
+                   help="also time run_until_stable with compaction off and on, alternated (a second JSON line)")
     a = p.parse_args()
     nat = pconv.native
     w, h, n = a.width, a.height, a.n
@@ -113,6 +120,39 @@ def main():
         "run_until_stable_median_ms": round(med(stable), 4), "run_max_reps_median_ms": round(med(fixed), 4),
         "reps_done": [int(s[0]) for s in infos], "converged": [bool(s[1]) for s in infos],
         "checks": max(int(s[3]) for s in infos),
+    }))
+
+    if not a.compact:
+        return
+    # Compaction off and on, alternated in this one process (one warm pass of
+    # each first: a compacted launch never tunes, it runs the model's tile or
+    # the tuned entry of its own image count).
+    loops = {False: [], True: []}
+    image_launches, launches, results = {}, {}, {}
+    for it in range(a.iters + 1):
+        for compact in (False, True):
+            beng.upload(flat, n)
+            beng.synchronize()
+            t0 = time.perf_counter()
+            results[compact] = beng.run_until_stable(a.max_reps, k, n, compact=compact)
+            ms = (time.perf_counter() - t0) * 1e3
+            if it > 0:
+                loops[compact].append(ms)
+            image_launches[compact] = int(beng.stats.image_launches)
+            launches[compact] = int(beng.stats.launches)
+    assert results[True] == results[False], "compaction changed the per-image results"
+
+    def mmm(xs):
+        return [round(min(xs), 4), round(med(xs), 4), round(max(xs), 4)]
+
+    print(json.dumps({
+        "shape": f"{n} x {w}x{h} {a.channels}", "filter": a.filter, "border": a.border, "fuse": fuse,
+        "check_every": k, "max_reps": a.max_reps,
+        "loop_off_ms": r(loops[False]), "loop_compact_ms": r(loops[True]),
+        "loop_off_min_median_max_ms": mmm(loops[False]), "loop_compact_min_median_max_ms": mmm(loops[True]),
+        "launches_off": launches[False], "launches_compact": launches[True],
+        "image_launches_off": image_launches[False], "image_launches_compact": image_launches[True],
+        "tuned": [[list(map(int, key)), list(map(int, shape))] for key, shape in nat.swar_tuned()],
     }))
 
 
