@@ -1,6 +1,7 @@
 // Batch engine: up to `capacity` whole images of ONE geometry resident on one
-// GPU, advanced together — every launch carries StencilLaunch::batch = n, so a
-// run of `reps` repetitions is ceil(reps / fuse) launches whatever n.
+// GPU, advanced together — every launch carries the n frames as its image set
+// (StencilLaunch::images, pconv/kernels.hpp), so a run of `reps` repetitions is
+// ceil(reps / fuse) launches whatever n.
 //
 // Small images cannot fill 256 CUs one at a time (a launch of the temporal
 // kernels costs its per-step latency, not its work: docs/PERFORMANCE.md §1.5);
@@ -20,7 +21,7 @@
 // Compaction (run_until_stable's `compact`, off by default): an image found
 // fixed at check j is retired — from check j + 1 and chunk j + 2 on, the fused
 // and the residual launches carry a table of the open images only
-// (StencilLaunch::active) and their grids shrink to those images.  The chunk
+// (ImageSet::active) and their grids shrink to those images.  The chunk
 // in flight while check j was read still holds the image, which is what makes
 // both of its ping-pong frames equal (see run_until_stable in the .cpp), so
 // results, downloads and later runs are those of compact = false, byte for
@@ -30,7 +31,7 @@
 //
 // Mixed sizes: the engine's geometry is then an ENVELOPE.  upload_sized puts
 // images of any sizes within it top-left into their frames and hands every
-// launch a table of their extents (StencilLaunch::dims): each image is
+// launch a table of their extents (ImageSet::dims): each image is
 // convolved as a lone image of its own size, in the same ceil(reps / fuse)
 // launches.  No frame is cleared in between — the kernels read nothing outside
 // an image, so a larger image's stale bytes never leak.  The mode lasts until
@@ -135,10 +136,25 @@ class BatchEngine {
   const RunStats& last_stats() const { return stats_; }
 
  private:
+  // A table the launches read on the device: the pinned words it is copied out
+  // of, the device region of `capacity` entries, and the event behind the
+  // latest copy.  Allocated by the first stage(), never on a capturing stream.
+  struct StagedTable {
+    PinnedBuffer pin;
+    DeviceBuffer dev;
+    Event ev;
+  };
+
   void check_n(const char* who, int n) const;
-  void set_dims(StencilLaunch& a) const;
-  void set_active(StencilLaunch& a) const;
+  // Flat copy / memset on the compute stream.
+  void copy_words(uint8_t* dst, const uint8_t* src, size_t bytes, hipMemcpyKind kind);
+  void zero_words(uint8_t* p, size_t bytes);
+  // One pitched copy per image between `packed` and the current frames.
+  void copy_images(bool to_frames, uint8_t* packed, int n, const ImageDims* extents, bool device);
+  // Rewrite `t` with n entries of entry_bytes each (`what` names it in errors).
+  void stage(StagedTable& t, const char* what, const void* entries, size_t entry_bytes, size_t n);
   void upload_active(const std::vector<int32_t>& table);
+  StencilLaunch base_launch(int n) const;
   void launch_batch_residual(int n);
   void enqueue_residual(int n);
   std::vector<uint64_t> finish_residual(int n);
@@ -155,23 +171,16 @@ class BatchEngine {
   PinnedBuffer res_host_;           // pinned words the running counts are read back into
   Event res_ev_;                    // the latest read-back has landed
   std::vector<uint64_t> res_seen_;  // the running counts at the latest check read
-  // Mixed sizes: the extents of the current upload_sized (empty: uniform), the
-  // pinned words they are copied out of, the device table of `capacity`
-  // entries (allocated on first use), and the event behind the latest copy.
+  // Mixed sizes: the extents of the current upload_sized (empty: uniform), as
+  // given, as the host copy the guards read, and on the device.
   std::vector<ImageSize> sizes_;
   std::vector<ImageDims> dims_host_;
-  PinnedBuffer dims_pin_;
-  DeviceBuffer dims_dev_;
-  Event dims_ev_;
+  StagedTable dims_;
   // Compaction: the open images of the run_until_stable in progress, in
-  // increasing order (empty: every launch covers images [0, n)) — the host
-  // copy the guards read —, the pinned words the table is copied out of, the
-  // device table of `capacity` entries (allocated on first use), and the event
-  // behind the latest copy.
+  // increasing order (empty: every launch covers images [0, n)): the host
+  // copy the guards read, and the device table.
   std::vector<int32_t> active_host_;
-  PinnedBuffer active_pin_;
-  DeviceBuffer active_dev_;
-  Event active_ev_;
+  StagedTable active_;
   Stream own_cs_;
   hipStream_t cs_ = nullptr;
   Event ev_t0_, ev_t1_, ev_sync_;

@@ -171,6 +171,14 @@ class Event {
   hipEvent_t e_ = nullptr;
 };
 
+// Whether `s` is being captured into a graph: nothing may be timed,
+// synchronised or allocated on it then (the engines tune a step's launches and
+// allocate their tables before they capture).
+inline bool stream_capturing(hipStream_t s) {
+  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+  return hipStreamIsCapturing(s, &st) == hipSuccess && st != hipStreamCaptureStatusNone;
+}
+
 // The copies behind the copy floors, set up once (device frames, pinned host
 // rows unless given, two streams; first-use costs paid in the constructor),
 // then timed on demand: run(n, up, down) issues n pitched H2D copies on one

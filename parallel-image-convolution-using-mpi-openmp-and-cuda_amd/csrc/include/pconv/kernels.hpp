@@ -36,6 +36,53 @@ struct ImageDims {
   int32_t height;
 };
 
+// The images of one launch (temporal kernels and the residual kernel): which
+// frames exist, which of them the grid covers, and how much of each frame is
+// image.  Every other field of StencilLaunch describes ONE frame and applies
+// to each.
+//   frames / stride: `frames` frames of that geometry lie `stride` bytes apart,
+// in src and dst alike (the residual kernel's counters number the same); frame
+// b starts b * stride after frame 0.  More than one frame needs a 16-byte
+// aligned stride that holds a whole frame.  Images never read each other's
+// rows: the set only moves the base pointers.
+//   active / active_host / count: optional table of `count` strictly increasing
+// frame indices inside [0, frames).  With it the grid is `count` images wide
+// and its k-th image is frame active[k]; frames the table does not name are
+// neither read nor written, and their counters are not touched.  Without it
+// the grid covers every frame in order (`count` is not read).  A launch with a
+// table runs its model's tile (or the tuned entry of its own key, if one
+// exists) and never starts first-use tuning.
+//   dims / dims_host: optional table of `frames` extents, indexed by FRAME.
+// With it the launch's geometry is the ENVELOPE all frames share and frame b's
+// image occupies rows [0, dims[b].height) and bytes [0, dims[b].row_bytes),
+// top-left aligned.  It is convolved exactly as a lone image of that size
+// under either border: whatever the rest of its frame holds reads as
+// out-of-image, and nothing of the destination frame outside the image is
+// written.  Whole images only (g_row0 = 0, r0 = 0, r1 = height).
+//   Each table is device memory the kernels read (they clamp every entry, to
+// frames - 1 and to the envelope, so a wrong table stays inside the
+// allocation) plus the host copy of the same entries the guards and tuners
+// read; both pointers or neither.
+struct ImageSet {
+  int frames = 1;
+  int64_t stride = 0;
+  const int32_t* active = nullptr;
+  const int32_t* active_host = nullptr;
+  int count = 0;
+  const ImageDims* dims = nullptr;
+  const ImageDims* dims_host = nullptr;
+
+  bool has_table() const { return active || active_host; }
+  bool has_dims() const { return dims || dims_host; }
+  // Images in the grid, and the frame of its k-th image (after the guards).
+  int images() const { return has_table() ? count : frames; }
+  int frame_of(int k) const { return active_host ? active_host[k] : k; }
+  // Entries of dims / dims_host.
+  int dims_entries() const { return frames; }
+  // One plain image: nothing here that only the temporal kernels read.
+  bool single() const { return frames <= 1 && !has_table() && !has_dims(); }
+};
+
 struct StencilLaunch {
   const uint8_t* src = nullptr;  // frame: owned row 0, data column 0
   uint8_t* dst = nullptr;        // same layout as src
@@ -51,43 +98,7 @@ struct StencilLaunch {
   // kernels only (they apply it at every fused step): Auto routes every step
   // count to them, the single-step variants reject it.
   Border border = Border::Zero;
-  // Image batch (temporal kernels and the residual kernel): `batch` independent images of this
-  // geometry advance in the one launch.  Every other field describes ONE image
-  // and applies to each; image b's frame lies b * batch_stride bytes after
-  // image 0's, in src and dst alike (ignored when batch == 1).  Images never
-  // read each other's rows: the batch only moves the base pointers.
-  int batch = 1;
-  int64_t batch_stride = 0;
-  // Mixed sizes (temporal kernels and the residual kernel): every field above
-  // is then the ENVELOPE all frames share, and image b occupies rows
-  // [0, dims[b].height) and bytes [0, dims[b].row_bytes) of its frame, top-left
-  // aligned.  It is convolved exactly as a lone image of that size under
-  // either border: whatever the rest of its frame holds (pad columns, ghost
-  // rows, a larger image's stale bytes) reads as out-of-image, and nothing of
-  // the destination frame outside the image is written.  `dims` is device
-  // memory of `batch` entries (the kernels clamp each entry to the envelope),
-  // `dims_host` the host copy of the same entries the guards read; both or
-  // neither.  Null: every image is the envelope.  Whole images only
-  // (g_row0 = 0, r0 = 0, r1 = height); batch = 1 is allowed.
-  const ImageDims* dims = nullptr;
-  const ImageDims* dims_host = nullptr;
-  // Active images (temporal kernels and the residual kernel): a launch over
-  // SOME of the `batch_frames` frames that lie batch_stride apart.  `batch` is
-  // then the number of table entries and the grid is that many images wide;
-  // entry k is the frame index of the grid's k-th image, whose frame lies
-  // active[k] * batch_stride after frame 0 (in src and dst alike; the residual
-  // kernel adds to counter[active[k]]).  Frames the table does not name are
-  // neither read nor written, and their counters are not touched.  The entries
-  // are strictly increasing inside [0, batch_frames).  `active` is device
-  // memory (the kernels clamp each entry to batch_frames - 1), `active_host`
-  // the host copy the guards read; both or neither.  `dims` stays indexed by
-  // FRAME: with a table it has batch_frames entries.  Null: image k is frame k
-  // and batch_frames is ignored.  A launch with a table runs its model's tile
-  // (or the tuned entry of its own key, if one exists) and never starts
-  // first-use tuning.
-  const int32_t* active = nullptr;
-  const int32_t* active_host = nullptr;
-  int batch_frames = 1;
+  ImageSet images;
 };
 
 enum class KernelVariant : int {
@@ -123,20 +134,16 @@ void prepare_float_temporal(const Filter& f, Channels ch, const StencilLaunch& a
 // Residual of the iterated map at the frame `a.src` (kernels/residual.hip):
 // one repetition of `f` under `a.border` is evaluated in registers for rows
 // [a.r0, a.r1) and the bytes of [0, row_bytes) with step(x) != x are counted.
-// Nothing is stored but the count, ADDED to *counter (device memory, zeroed by
+// Nothing is stored but the count, ADDED to a counter (device memory, zeroed by
 // the caller): zero means the rows are a fixed point of the repetition.  Reads
-// src, pitch, row_bytes, r0, r1, frame_lo, frame_hi, g_row0, height, border,
-// batch and batch_stride (dst and steps are ignored); the rows are clipped to
-// the global image and validated against the frame like a one-step
-// launch_stencil.
-// Image batch: `counter` points at a.batch consecutive 64-bit counters and
-// image b's count (its frame b * batch_stride bytes after image 0's) is ADDED
-// to counter[b], all in the one launch; no counter beyond a.batch is touched.
-// The batch guards are launch_stencil's (check_batch), every geometry guard
-// holds per image, and batch x workgroups per image must stay below 2^31.
-// With an active-image table (a.active) `counter` points at a.batch_frames
-// counters, the grid's k-th image adds to counter[active[k]], and the counters
-// of frames the table does not name are not touched.
+// src, pitch, row_bytes, r0, r1, frame_lo, frame_hi, g_row0, height, border
+// and images (dst and steps are ignored); the rows are clipped to the global
+// image and validated against the frame like a one-step launch_stencil.
+// `counter` points at a.images.frames consecutive 64-bit counters: the count of
+// every image of the grid is ADDED to its FRAME's counter, all in the one
+// launch, and no other counter is touched.  The image-set guards are
+// launch_stencil's, every geometry guard holds per image, and images x
+// workgroups per image must stay below 2^31.
 void launch_residual(const Filter& f, Channels ch, const StencilLaunch& a, uint64_t* counter, hipStream_t stream);
 // Rows one workgroup of the residual kernel covers (tests place image heights around it).
 constexpr int kResidualBlockRows = 32;
@@ -203,7 +210,7 @@ void clear_swar_tuning();
 void clear_float_tuning();
 // Tuned SWAR entries: ({channels, steps, rows, row_bytes, step_form, kernel, batch, live}, shape); kernel 0: the
 // tile kernel k_swar, 1: the buffer-op tile kernel k_swar_pf; live: the workgroups of a mixed-size launch
-// (StencilLaunch::dims) that have output in their image, 0 for a uniform launch.
+// (ImageSet::dims) that have output in their image, 0 for a uniform launch.
 std::vector<std::pair<std::vector<int64_t>, SwarShape>> swar_tuned();
 
 }  // namespace pconv

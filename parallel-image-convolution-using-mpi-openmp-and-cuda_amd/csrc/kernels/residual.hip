@@ -13,7 +13,7 @@
 // workgroup's four waves through LDS, and one 64-bit atomic add per workgroup
 // (none when its count is zero) lands on the device counter.
 //
-// An image batch (StencilLaunch::batch) is a run-time argument, as in the
+// An image batch (StencilLaunch::images) is a run-time argument, as in the
 // temporal kernels: the flat grid is batch x blocks_per_image workgroups,
 // image-major, so a workgroup never spans two images.  Its image comes from
 // the workgroup id (scalar) and does two things only: it moves the frame
@@ -33,6 +33,7 @@
 
 #include "pconv/device.hpp"
 #include "pconv/kernels.hpp"
+#include "image_set.hpp"
 #include "nine_tap.hpp"
 #include "tuning.hpp"
 
@@ -171,20 +172,20 @@ void launch_ch(const Filter& f, const StencilLaunch& a, uint64_t* counter, hipSt
   const auto [lo, hi] = image_rows_in_frame(a);
   const int64_t bx = ceil_div<int64_t>(ceil_div<int64_t>(a.row_bytes, 16), 64);
   const int64_t by = ceil_div<int64_t>(rows, kResidualBlockRows);
-  PCONV_CHECK(bx * by < (int64_t(1) << 31) && bx * by * a.batch < (int64_t(1) << 31),
+  const int images = a.images.images();
+  PCONV_CHECK(bx * by < (int64_t(1) << 31) && bx * by * images < (int64_t(1) << 31),
               "launch_residual: too many workgroups for one grid (batch x blocks per image)");
   const Taps9 tp = make_taps9(f);
-  const dim3 grid(static_cast<unsigned>(bx * by * a.batch)), block(64, 4);
+  const dim3 grid(static_cast<unsigned>(bx * by * images)), block(64, 4);
   auto* ctr = reinterpret_cast<unsigned long long*>(counter);
   const int rb = static_cast<int>(a.row_bytes), r0 = static_cast<int>(a.r0), r1 = static_cast<int>(a.r1);
   const int nbx = static_cast<int>(bx), per_image = static_cast<int>(bx * by), img_lo = lo, img_hi = hi;
-  const int64_t stride = a.batch > 1 || a.active ? a.batch_stride : int64_t(0);
-  const unsigned last_frame = a.active ? static_cast<unsigned>(a.batch_frames - 1) : 0u;
+  const BatchKernelArgs b = batch_kernel_args(a);
   with_bool(!int_form_allowed(f), [&](auto fl) {
     with_bool(a.border == Border::Replicate, [&](auto rep) {
       k_residual<CH, decltype(fl)::value, decltype(rep)::value>
-          <<<grid, block, 0, s>>>(a.src, a.pitch, rb, r0, r1, tp, img_lo, img_hi, nbx, per_image, stride, ctr,
-                                  a.dims, a.active, last_frame);
+          <<<grid, block, 0, s>>>(a.src, a.pitch, rb, r0, r1, tp, img_lo, img_hi, nbx, per_image, b.stride, ctr,
+                                  b.dims, b.active, b.last_frame);
     });
   });
 }
@@ -193,15 +194,13 @@ void launch_ch(const Filter& f, const StencilLaunch& a, uint64_t* counter, hipSt
 
 void launch_residual(const Filter& f, Channels ch, const StencilLaunch& a_in, uint64_t* counter, hipStream_t stream) {
   StencilLaunch a = a_in;
-  check_active("launch_residual", a);  // before anything reads the table's entries
-  check_dims("launch_residual", a, channel_count(ch));  // on the rows as given: whole images
+  check_image_set("launch_residual", a, channel_count(ch));  // on the rows as given
   // rows outside the global image are no part of the map (launch_stencil's clip)
   a.r0 = std::max(a.r0, -a.g_row0);
   a.r1 = std::min(a.r1, a.height - a.g_row0);
   if (a.r1 <= a.r0) return;
   // Geometry guards: every access of the launch must stay inside the frame.
   PCONV_CHECK(a.row_bytes >= 1, "launch_residual: empty rows");
-  check_batch("launch_residual", a);
   check_frame_access("launch_residual", a, a.src && counter, 1);
   PCONV_CHECK(reinterpret_cast<uintptr_t>(a.src) % 16 == 0, "launch_residual: frame rows must be 16-byte aligned");
   PCONV_CHECK(a.row_bytes < (int64_t(1) << 31) - 2048 && a.r1 - a.frame_lo < (int64_t(1) << 31) - 64 &&

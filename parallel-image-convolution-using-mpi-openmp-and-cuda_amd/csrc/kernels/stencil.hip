@@ -21,6 +21,7 @@
 
 #include "pconv/kernels.hpp"
 #include "pconv/device.hpp"
+#include "image_set.hpp"
 #include "nine_tap.hpp"
 #include "swar.hpp"
 #include "tuning.hpp"
@@ -245,15 +246,13 @@ namespace {
 //   The single-step kernels take their boundary from the frame's zero pad: a
 // non-zero border runs on the temporal kernels for every step count (an
 // int_exact filter is bit-identical in the float kernel by definition), and
-// so does an image batch: only the temporal kernels' grids carry one; and so
-// does a launch with per-image extents (dims) or an active-image table
-// (active), which only they read.
+// so does every launch whose image set (StencilLaunch::images) is more than
+// one plain image: only the temporal kernels' grids carry one.
 bool resolve_launch(const Filter& f, StencilLaunch& a, KernelVariant& v) {
   a.r0 = std::max(a.r0, -a.g_row0);
   a.r1 = std::min(a.r1, a.height - a.g_row0);
   if (a.r1 <= a.r0) return false;
-  const bool fused = a.steps > 1 || a.border != Border::Zero || a.batch > 1 || a.dims || a.dims_host || a.active ||
-                     a.active_host;
+  const bool fused = a.steps > 1 || a.border != Border::Zero || !a.images.single();
   if (v == KernelVariant::Auto)
     v = f.binomial121 ? (fused ? KernelVariant::Temporal : KernelVariant::Binomial)
                       : (fused ? KernelVariant::FloatTemporal
@@ -268,7 +267,7 @@ bool resolve_launch(const Filter& f, StencilLaunch& a, KernelVariant& v) {
 void prepare_stencil(const Filter& f, Channels ch, const StencilLaunch& a_in, hipStream_t stream, KernelVariant v) {
   StencilLaunch a = a_in;
   if (!resolve_launch(f, a, v) || a.steps > kMaxFusedSteps) return;
-  if (a.active || a.active_host) return;  // an active-image launch never tunes: nothing to settle
+  if (a.images.has_table()) return;  // an active-image launch never tunes: nothing to settle
   if (v == KernelVariant::Temporal && f.binomial121) prepare_swar(a, ch, stream);
   if (v == KernelVariant::FloatTemporal) prepare_float_temporal(f, ch, a, stream);
 }
@@ -281,23 +280,15 @@ void launch_stencil(const Filter& f, Channels ch, const StencilLaunch& a_in, hip
   check_frame_access("launch_stencil", a, a.src && a.dst && a.src != a.dst, a.steps);
   PCONV_CHECK(a.row_bytes < (int64_t(1) << 31) && a.r1 - a.frame_lo < (int64_t(1) << 31),
               "launch_stencil: geometry exceeds 32-bit kernel indices");
-  check_batch("launch_stencil", a);
-  PCONV_CHECK((!a.active && !a.active_host) || v == KernelVariant::Temporal || v == KernelVariant::FloatTemporal,
-              "launch_stencil: active not supported by kernel '" + std::string(kernel_variant_name(v)) +
-                  "' (temporal and float_temporal only)");
-  check_active("launch_stencil", a);  // before anything reads the table's entries
-  PCONV_CHECK((!a.dims && !a.dims_host) || v == KernelVariant::Temporal || v == KernelVariant::FloatTemporal,
-              "launch_stencil: dims not supported by kernel '" + std::string(kernel_variant_name(v)) +
-                  "' (temporal and float_temporal only)");
-  check_dims("launch_stencil", a_in, channel_count(ch));  // on the rows as given: whole images
-  PCONV_CHECK(a.batch == 1 || v == KernelVariant::Temporal || v == KernelVariant::FloatTemporal,
-              "launch_stencil: batch not supported by kernel '" + std::string(kernel_variant_name(v)) +
-                  "' (temporal and float_temporal only)");
-  PCONV_CHECK(a.border == Border::Zero || v == KernelVariant::Temporal || v == KernelVariant::FloatTemporal,
-              "launch_stencil: border '" + std::string(border_name(a.border)) + "' not supported by kernel '" +
-                  std::string(kernel_variant_name(v)) + "' (temporal and float_temporal only)");
+  check_image_set("launch_stencil", a_in, channel_count(ch));  // on the rows as given
+  if (v != KernelVariant::Temporal && v != KernelVariant::FloatTemporal)
+    check_temporal_only("launch_stencil", kernel_variant_name(v),
+                        {{"active", a.images.has_table()},
+                         {"dims", a.images.has_dims()},
+                         {"batch", a.images.frames != 1},
+                         {"border '" + std::string(border_name(a.border)) + "'", a.border != Border::Zero}});
   if (v == KernelVariant::FloatTemporal) {
-    launch_float_temporal(f, ch, a, stream);
+    launch_float_temporal_checked(f, ch, a, stream);
     PCONV_HIP_CHECK(hipGetLastError());
     return;
   }

@@ -37,6 +37,7 @@
 
 #include "pconv/device.hpp"
 #include "pconv/kernels.hpp"
+#include "image_set.hpp"
 #include "tuning.hpp"
 
 namespace pconv {
@@ -512,18 +513,19 @@ FloatShape pick_ft_shape(int steps, int ch, int64_t rows, int64_t row_bytes, int
 
 template <int CH, bool UNIFORM, int M, int NW>
 void launch_ft_shape(const StencilLaunch& a, const FloatTaps& tp, hipStream_t s) {
-  const FtGeom g = ft_geom(FloatShape{M, NW}, CH, a.steps, a.r1 - a.r0, a.row_bytes, a.batch);
+  const int images = a.images.images();
+  const BatchKernelArgs b = batch_kernel_args(a);
+  const FtGeom g = ft_geom(FloatShape{M, NW}, CH, a.steps, a.r1 - a.r0, a.row_bytes, images);
   PCONV_CHECK(g.ok, "float temporal kernel: steps too large for the tile");
   PCONV_CHECK(g.tiles < (int64_t(1) << 31), "float temporal kernel: too many tiles (batch x tiles per image)");
   const dim3 grid(static_cast<unsigned>(g.col_tiles), static_cast<unsigned>(g.row_tiles),
-                  static_cast<unsigned>(a.batch));
+                  static_cast<unsigned>(images));
   const auto kern = a.border == Border::Replicate ? &k_float_temporal<CH, UNIFORM, M, NW, true>
                                                   : &k_float_temporal<CH, UNIFORM, M, NW, false>;
   kern<<<grid, dim3(64 * NW), 0, s>>>(
       a.src, a.dst, a.pitch, static_cast<int>(a.row_bytes), static_cast<int>(a.r0), static_cast<int>(a.r1), a.steps,
       static_cast<int>(a.g_row0), static_cast<int>(std::min<int64_t>(a.height, int64_t(1) << 30)), tp,
-      a.batch > 1 || a.active ? a.batch_stride : int64_t(0), a.dims, a.active,
-      a.active ? static_cast<unsigned>(a.batch_frames - 1) : 0u);
+      b.stride, b.dims, b.active, b.last_frame);
 }
 
 template <int CH, bool UNIFORM>
@@ -562,11 +564,12 @@ std::map<FtKey, FloatShape> g_ft_tuned;
 template <int CH, bool UNIFORM>
 FloatShape tuned_ft_shape(const StencilLaunch& a, const FloatTaps& tp, hipStream_t s) {
   const int64_t rows = a.r1 - a.r0;
-  const FloatShape model = pick_ft_shape(a.steps, CH, rows, a.row_bytes, a.batch);
+  const int images = a.images.images();
+  const FloatShape model = pick_ft_shape(a.steps, CH, rows, a.row_bytes, images);
   if (g_ft_force_m.load(std::memory_order_relaxed) || !shape_tuning_enabled()) return model;
   // (the model saw the envelope: an early-exiting workgroup is charged as a full one)
-  const FtGeom mg = ft_geom(model, CH, a.steps, rows, a.row_bytes, a.batch);
-  const FtKey key{CH, UNIFORM, a.steps, rows, a.row_bytes, a.batch,
+  const FtGeom mg = ft_geom(model, CH, a.steps, rows, a.row_bytes, images);
+  const FtKey key{CH, UNIFORM, a.steps, rows, a.row_bytes, images,
                   live_workgroups(a, int64_t(mg.vlanes) * 8, mg.vrows, 1)};
   {
     std::lock_guard<std::mutex> lk(g_ft_mu);
@@ -574,7 +577,7 @@ FloatShape tuned_ft_shape(const StencilLaunch& a, const FloatTaps& tp, hipStream
     if (it != g_ft_tuned.end()) return it->second;
   }
   // (an active-image launch never tunes: its own cached entry above, else the model; stencil_swar.hip)
-  if (stream_capturing(s) || a.active) return model;
+  if (stream_capturing(s) || a.images.has_table()) return model;
   std::vector<FloatShape> ok;
   for (const auto& c : kFtShapes)
     if (ft_geom(c, CH, a.steps, rows, a.row_bytes).ok) ok.push_back(c);
@@ -596,10 +599,8 @@ void float_temporal(const Filter& f, Channels ch, const StencilLaunch& a, hipStr
   PCONV_CHECK(a.steps >= 1 && a.steps <= kMaxFusedSteps, "float temporal kernel: steps out of range");
   PCONV_CHECK(a.height < (int64_t(1) << 30) && a.g_row0 < (int64_t(1) << 30), "float temporal kernel: rows exceed 2^30");
   PCONV_CHECK(a.row_bytes > 0 && a.row_bytes < (int64_t(1) << 30), "float temporal kernel: row bytes out of range");
-  check_batch("launch_float_temporal", a);
-  check_active("launch_float_temporal", a);
-  check_dims("launch_float_temporal", a, channel_count(ch));
-  PCONV_CHECK(a.batch <= 65535, "launch_float_temporal: batch " + std::to_string(a.batch) + " exceeds grid.z (65535)");
+  PCONV_CHECK(a.images.images() <= 65535,
+              "launch_float_temporal: batch " + std::to_string(a.images.images()) + " exceeds grid.z (65535)");
   FloatTaps tp;
   bool uniform = true;
   for (int i = 0; i < 9; ++i) {
@@ -617,11 +618,17 @@ void float_temporal(const Filter& f, Channels ch, const StencilLaunch& a, hipStr
 
 }  // namespace
 
+void launch_float_temporal_checked(const Filter& f, Channels ch, const StencilLaunch& a, hipStream_t stream) {
+  float_temporal(f, ch, a, stream, true);
+}
+
 void launch_float_temporal(const Filter& f, Channels ch, const StencilLaunch& a, hipStream_t stream) {
+  check_image_set("launch_float_temporal", a, channel_count(ch));
   float_temporal(f, ch, a, stream, true);
 }
 
 void prepare_float_temporal(const Filter& f, Channels ch, const StencilLaunch& a, hipStream_t stream) {
+  check_image_set("launch_float_temporal", a, channel_count(ch));
   float_temporal(f, ch, a, stream, false);
 }
 

@@ -55,6 +55,7 @@
 #include <vector>
 
 #include "pconv/device.hpp"
+#include "image_set.hpp"
 #include "swar.hpp"
 #include "swar_device.hpp"
 #include "tuning.hpp"
@@ -475,9 +476,10 @@ SwarGeom swar_geom(const SwarShape& sh, int ch, int steps, int64_t rows, int64_t
 // Whole dwords per row of every image of a mixed-size launch (true without
 // dims); with an active-image table, of the frames it names.
 bool pf_dims_ok(const StencilLaunch& a) {
-  if (a.dims_host)
-    for (int b = 0; b < a.batch; ++b)
-      if (a.dims_host[frame_of(a, b)].row_bytes % 4 != 0) return false;
+  const ImageSet& s = a.images;
+  if (s.dims_host)
+    for (int k = 0; k < s.images(); ++k)
+      if (s.dims_host[s.frame_of(k)].row_bytes % 4 != 0) return false;
   return true;
 }
 
@@ -495,7 +497,8 @@ template <int CH, size_t I, bool PF>
 void launch_tile(const StencilLaunch& a, hipStream_t s, int form) {
   constexpr SwarShape S = kTiles[I].shape;
   const char* who = PF ? "swar prefetch kernel" : "swar temporal kernel";
-  const SwarGeom g = swar_geom(S, CH, a.steps, a.r1 - a.r0, a.row_bytes, a.batch);
+  const SwarGeom g = swar_geom(S, CH, a.steps, a.r1 - a.r0, a.row_bytes, a.images.images());
+  const BatchKernelArgs b = batch_kernel_args(a);
   PCONV_CHECK(g.ok, std::string(who) + ": steps too large for the tile");
   if constexpr (PF)
     PCONV_CHECK(pf_launch_ok(a, a.steps), std::string(who) + ": needs whole dwords per row and < 2 GiB ranges");
@@ -507,9 +510,7 @@ void launch_tile(const StencilLaunch& a, hipStream_t s, int form) {
                                 static_cast<int>(a.r1), a.steps, static_cast<int>(a.g_row0), hmax,
                                 static_cast<int>(g.nstrips), static_cast<int>(g.pair_stride),
                                 static_cast<int>(g.row_tiles), xcd_swizzle_enabled() ? 1 : 0,
-                                static_cast<int>(g.tiles_per_image),
-                                a.batch > 1 || a.active ? a.batch_stride : int64_t(0), a.dims, a.active,
-                                a.active ? static_cast<unsigned>(a.batch_frames - 1) : 0u);
+                                static_cast<int>(g.tiles_per_image), b.stride, b.dims, b.active, b.last_frame);
   };
   if constexpr (PF)
     launch(swar_pf_kernel<CH, S.m, S.nw>(form, a.border), static_cast<int>(a.pitch));
@@ -722,7 +723,7 @@ std::atomic<int> g_shape_tuning{1};     // first-use tuning of both temporal ker
 std::atomic<int> g_tune_candidates{6};  // model-ranked shapes timed per launch geometry
 
 SwarChoice tuned_choice(const StencilLaunch& a, Channels ch, hipStream_t stream, bool may_measure) {
-  const int c = channel_count(ch);
+  const int c = channel_count(ch), images = a.images.images();
   const int64_t rows = a.r1 - a.r0;
   const int mode = alt_mode();
   const auto runs = [&](const SwarShape& sh) { return swar_geom(sh, c, a.steps, rows, a.row_bytes).tiles > 0; };
@@ -745,22 +746,22 @@ SwarChoice tuned_choice(const StencilLaunch& a, Channels ch, hipStream_t stream,
       fallback.kern = 1;
       return fallback;
     }
-    fallback.shape = pick_swar_shape(a.steps, c, rows, a.row_bytes, a.batch);
+    fallback.shape = pick_swar_shape(a.steps, c, rows, a.row_bytes, images);
     return fallback;
   }
   if (override_shape(fallback.shape) || !shape_tuning_enabled()) {
-    if (!override_shape(fallback.shape)) fallback.shape = pick_swar_shape(a.steps, c, rows, a.row_bytes, a.batch);
+    if (!override_shape(fallback.shape)) fallback.shape = pick_swar_shape(a.steps, c, rows, a.row_bytes, images);
     return fallback;
   }
   // The model is asked with the envelope and the batch: a workgroup that
   // leaves early in a smaller image is charged as a full one.
   int64_t live = 0;
-  if (a.dims_host) {
-    const SwarGeom mg = swar_geom(pick_swar_shape(a.steps, c, rows, a.row_bytes, a.batch), c, a.steps, rows,
-                                  a.row_bytes, a.batch);
+  if (a.images.dims_host) {
+    const SwarGeom mg = swar_geom(pick_swar_shape(a.steps, c, rows, a.row_bytes, images), c, a.steps, rows,
+                                  a.row_bytes, images);
     live = live_workgroups(a, mg.vbytes, mg.vrows, 2);
   }
-  const TuneKey key{c, a.steps, rows, a.row_bytes, a.batch, live};
+  const TuneKey key{c, a.steps, rows, a.row_bytes, images, live};
   {
     std::lock_guard<std::mutex> lk(g_tune_mu);
     auto it = g_tuned.find(key);
@@ -770,15 +771,15 @@ SwarChoice tuned_choice(const StencilLaunch& a, Channels ch, hipStream_t stream,
       return r;
     }
   }
-  fallback.shape = pick_swar_shape(a.steps, c, rows, a.row_bytes, a.batch);
+  fallback.shape = pick_swar_shape(a.steps, c, rows, a.row_bytes, images);
   // A launch with an active-image table never tunes: the live counts of a
   // compacting loop are arbitrary, and a dozen timed candidates per count
   // would cost more than the retired images save.  It ran the cached entry of
   // its own key above if there was one; else the model's pick for its grid.
-  if (!may_measure || stream_capturing(stream) || a.active) return fallback;
+  if (!may_measure || stream_capturing(stream) || a.images.has_table()) return fallback;
   std::vector<std::pair<double, SwarShape>> ranked;
   for (const auto& t : kTiles) {
-    const double cost = swar_launch_cycles(t.shape, a.steps, c, rows, a.row_bytes, a.batch);
+    const double cost = swar_launch_cycles(t.shape, a.steps, c, rows, a.row_bytes, images);
     if (cost < 1e299) ranked.emplace_back(cost, t.shape);
   }
   PCONV_CHECK(!ranked.empty(), "swar temporal kernel: steps too large for every tile shape");

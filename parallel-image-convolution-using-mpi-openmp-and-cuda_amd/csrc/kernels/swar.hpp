@@ -8,7 +8,7 @@
 namespace pconv {
 
 // Latency model of one launch (cycles) and the shape it picks; the grid is
-// `batch` images of rows x row_bytes (StencilLaunch::batch).
+// `batch` images of rows x row_bytes (ImageSet::images()).
 double swar_launch_cycles(SwarShape s, int steps, int ch, int64_t rows, int64_t row_bytes, int batch = 1);
 SwarShape pick_swar_shape(int steps, int ch, int64_t rows, int64_t row_bytes, int batch = 1);
 

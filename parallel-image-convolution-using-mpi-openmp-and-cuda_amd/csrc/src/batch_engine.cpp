@@ -37,10 +37,7 @@ BatchEngine::BatchEngine(const ImageGeom& geom, const Filter& filter, int capaci
   // of images a partial batch leaves out are never written afterwards.
   for (auto& f : frame_) {
     f = DeviceBuffer(static_cast<size_t>(stride_ * capacity_));
-    if (opt_.kernel_copies)
-      launch_fill_zero(f.data(), static_cast<int64_t>(f.size()), cs_);
-    else
-      PCONV_HIP_CHECK(hipMemsetAsync(f.data(), 0, f.size(), cs_));
+    zero_words(f.data(), f.size());
   }
   ev_sync_ = Event::create();
   ev_t0_ = Event::create(true);
@@ -60,124 +57,98 @@ void BatchEngine::check_n(const char* who, int n) const {
                   std::to_string(sizes_.size()));
 }
 
-// Mixed mode: the launch carries the extents table and its host copy.
-void BatchEngine::set_dims(StencilLaunch& a) const {
-  if (sizes_.empty()) return;
-  a.dims = reinterpret_cast<const ImageDims*>(dims_dev_.data());
-  a.dims_host = dims_host_.data();
+// ---- copies: one switch site per kind (opt_.kernel_copies: the CUs move the
+// bytes, no SDMA engine and no runtime blit program) -------------------------
+
+void BatchEngine::copy_words(uint8_t* dst, const uint8_t* src, size_t bytes, hipMemcpyKind kind) {
+  const int64_t b = static_cast<int64_t>(bytes);
+  if (opt_.kernel_copies)
+    launch_copy_rows(src, b, dst, b, b, 1, cs_);
+  else
+    PCONV_HIP_CHECK(hipMemcpyAsync(dst, src, bytes, kind, cs_));
 }
 
-// Compaction: the launch covers the open images only.  `batch` becomes the
-// number of table entries, the frames (and the extents table) stay the call's.
-void BatchEngine::set_active(StencilLaunch& a) const {
-  if (active_host_.empty()) return;
-  a.batch_frames = a.batch;
-  a.batch = static_cast<int>(active_host_.size());
-  a.active = reinterpret_cast<const int32_t*>(active_dev_.data());
-  a.active_host = active_host_.data();
+void BatchEngine::zero_words(uint8_t* p, size_t bytes) {
+  if (opt_.kernel_copies)
+    launch_fill_zero(p, static_cast<int64_t>(bytes), cs_);
+  else
+    PCONV_HIP_CHECK(hipMemsetAsync(p, 0, bytes, cs_));
 }
 
-// The table of open images goes to the device as the extents table does: out
-// of pinned words that are rewritten only after the event behind the previous
-// copy out of them, and copied ON THE COMPUTE STREAM.  One device region is
-// enough: the stream is in order, so the copy lands after every launch that
-// was enqueued with the previous table has finished, and before every launch
-// enqueued after it starts.
+// n pitched 2-D copies, one per image — the call every other engine of this
+// library uses for its rows — between the current frames and `packed`, where
+// the images lie back to back with tight rows; image b is extents[b], or the
+// engine's geometry for every image (null).  One hipMemcpy3DAsync could
+// describe a whole uniform batch (the frames sit a whole number of pitches
+// apart), but it has not been timed against this form; tools/batch_sweep.py
+// reports the end-to-end time these copies give.
+void BatchEngine::copy_images(bool to_frames, uint8_t* packed, int n, const ImageDims* extents, bool device) {
+  const hipMemcpyKind kind =
+      device ? hipMemcpyDeviceToDevice : (to_frames ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost);
+  for (int b = 0; b < n; ++b) {
+    const int64_t rb = extents ? extents[b].row_bytes : lay_.row_bytes, rows = extents ? extents[b].height : lay_.rows;
+    uint8_t* frame = frame_at(cur_) + b * stride_;  // cur_ follows the launches: the newest frames
+    const uint8_t* src = to_frames ? packed : frame;
+    uint8_t* dst = to_frames ? frame : packed;
+    const int64_t sp = to_frames ? rb : lay_.pitch, dp = to_frames ? lay_.pitch : rb;
+    if (opt_.kernel_copies)
+      launch_copy_rows(src, sp, dst, dp, rb, rows, cs_);
+    else
+      PCONV_HIP_CHECK(hipMemcpy2DAsync(dst, dp, src, sp, rb, rows, kind, cs_));
+    packed += rb * rows;
+  }
+}
+
+// A table goes to the device out of pinned words that are rewritten only after
+// the event behind the previous copy out of them, and is copied ON THE COMPUTE
+// STREAM.  One device region is enough: the stream is in order, so the copy
+// lands after every launch that was enqueued with the previous table has
+// finished, and before every launch enqueued after it starts.
+void BatchEngine::stage(StagedTable& t, const char* what, const void* entries, size_t entry_bytes, size_t n) {
+  const size_t bytes = round_up<size_t>(entry_bytes * static_cast<size_t>(capacity_), 16);
+  if (!t.dev.data()) {
+    PCONV_CHECK(!stream_capturing(cs_),
+                std::string("BatchEngine: the ") + what + " table cannot be allocated on a capturing stream");
+    t.dev = DeviceBuffer(bytes);
+    t.pin = PinnedBuffer(bytes);
+    std::memset(t.pin.data(), 0, bytes);
+    t.ev = Event::create();
+  } else {
+    t.ev.sync();  // the previous copy out of the pinned words has completed
+  }
+  std::memcpy(t.pin.data(), entries, entry_bytes * n);
+  copy_words(t.dev.data(), t.pin.data(), bytes, hipMemcpyHostToDevice);
+  t.ev.record(cs_);
+}
+
 void BatchEngine::upload_active(const std::vector<int32_t>& table) {
   PCONV_CHECK(!table.empty() && static_cast<int>(table.size()) <= capacity_,
               "BatchEngine: an active-image table must hold 1 to `capacity` entries");
-  const size_t bytes = round_up<size_t>(sizeof(int32_t) * static_cast<size_t>(capacity_), 16);
-  if (!active_dev_.data()) {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    PCONV_CHECK(hipStreamIsCapturing(cs_, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone,
-                "BatchEngine: the active-image table cannot be allocated on a capturing stream");
-    active_dev_ = DeviceBuffer(bytes);
-    active_pin_ = PinnedBuffer(bytes);
-    std::memset(active_pin_.data(), 0, bytes);
-    active_ev_ = Event::create();
-  } else {
-    active_ev_.sync();  // the previous copy out of the pinned words has completed
-  }
-  std::memcpy(active_pin_.data(), table.data(), sizeof(int32_t) * table.size());
-  if (opt_.kernel_copies)
-    launch_copy_rows(active_pin_.data(), static_cast<int64_t>(bytes), active_dev_.data(), static_cast<int64_t>(bytes),
-                     static_cast<int64_t>(bytes), 1, cs_);
-  else
-    PCONV_HIP_CHECK(hipMemcpyAsync(active_dev_.data(), active_pin_.data(), bytes, hipMemcpyHostToDevice, cs_));
-  active_ev_.record(cs_);
+  stage(active_, "active-image", table.data(), sizeof(int32_t), table.size());
   active_host_ = table;
 }
 
-// Copies: n pitched 2-D copies, one per image — the call every other engine of
-// this library uses for its rows.  One hipMemcpy3DAsync could describe the
-// whole batch (the frames sit a whole number of pitches apart), but it has not
-// been timed against this form; tools/batch_sweep.py reports the end-to-end
-// time these copies give.
 void BatchEngine::upload(const uint8_t* p, int n, bool device) {
   sizes_.clear();  // back to uniform launches
   dims_host_.clear();
   check_n("BatchEngine::upload", n);
   PCONV_CHECK(p != nullptr || n == 0, "BatchEngine::upload: null source");
-  const int64_t rb = lay_.row_bytes, img = geom_.bytes();
-  for (int b = 0; b < n; ++b) {
-    uint8_t* d = frame_at(cur_) + b * stride_;
-    if (opt_.kernel_copies)
-      launch_copy_rows(p + b * img, rb, d, lay_.pitch, rb, lay_.rows, cs_);
-    else
-      PCONV_HIP_CHECK(hipMemcpy2DAsync(d, lay_.pitch, p + b * img, rb, rb, lay_.rows,
-                                       device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, cs_));
-  }
+  copy_images(true, const_cast<uint8_t*>(p), n, nullptr, device);
 }
 
 void BatchEngine::download(uint8_t* p, int n, bool device) {
   check_n("BatchEngine::download", n);
   PCONV_CHECK(p != nullptr || n == 0, "BatchEngine::download: null destination");
-  const int64_t rb = lay_.row_bytes, img = geom_.bytes();
-  for (int b = 0; b < n; ++b) {
-    const uint8_t* s = frame_at(cur_) + b * stride_;  // cur_ follows the launches: the newest frames
-    if (opt_.kernel_copies)
-      launch_copy_rows(s, lay_.pitch, p + b * img, rb, rb, lay_.rows, cs_);
-    else
-      PCONV_HIP_CHECK(hipMemcpy2DAsync(p + b * img, rb, s, lay_.pitch, rb, lay_.rows,
-                                       device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, cs_));
-  }
+  copy_images(false, p, n, nullptr, device);
 }
 
 void BatchEngine::upload_sized(const uint8_t* p, const std::vector<ImageSize>& sizes, bool device) {
   std::vector<ImageDims> table = image_dims_table(geom_, capacity_, sizes);
   PCONV_CHECK(p != nullptr || sizes.empty(), "BatchEngine::upload_sized: null source");
-  if (sizes.empty()) {
-    sizes_.clear();
-    dims_host_.clear();
-    return;
-  }
-  const size_t bytes = round_up<size_t>(sizeof(ImageDims) * static_cast<size_t>(capacity_), 16);
-  if (!dims_dev_.data()) {
-    dims_dev_ = DeviceBuffer(bytes);
-    dims_pin_ = PinnedBuffer(bytes);
-    std::memset(dims_pin_.data(), 0, bytes);
-    dims_ev_ = Event::create();
-  } else {
-    dims_ev_.sync();  // the previous copy out of the pinned words has completed
-  }
-  std::memcpy(dims_pin_.data(), table.data(), sizeof(ImageDims) * table.size());
-  if (opt_.kernel_copies)
-    launch_copy_rows(dims_pin_.data(), static_cast<int64_t>(bytes), dims_dev_.data(), static_cast<int64_t>(bytes),
-                     static_cast<int64_t>(bytes), 1, cs_);
-  else
-    PCONV_HIP_CHECK(hipMemcpyAsync(dims_dev_.data(), dims_pin_.data(), bytes, hipMemcpyHostToDevice, cs_));
-  dims_ev_.record(cs_);
-  // No frame is cleared: the kernels read nothing outside an image.
-  const uint8_t* s = p;
-  for (size_t b = 0; b < sizes.size(); ++b) {
-    const int64_t rb = table[b].row_bytes, rows = table[b].height;
-    uint8_t* d = frame_at(cur_) + static_cast<int64_t>(b) * stride_;
-    if (opt_.kernel_copies)
-      launch_copy_rows(s, rb, d, lay_.pitch, rb, rows, cs_);
-    else
-      PCONV_HIP_CHECK(hipMemcpy2DAsync(d, lay_.pitch, s, rb, rb, rows,
-                                       device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, cs_));
-    s += rb * rows;
+  if (!sizes.empty()) {
+    stage(dims_, "extents", table.data(), sizeof(ImageDims), table.size());
+    // No frame is cleared: the kernels read nothing outside an image.
+    copy_images(true, const_cast<uint8_t*>(p), static_cast<int>(table.size()), table.data(), device);
   }
   sizes_ = sizes;
   dims_host_ = std::move(table);
@@ -185,17 +156,36 @@ void BatchEngine::upload_sized(const uint8_t* p, const std::vector<ImageSize>& s
 
 void BatchEngine::download_sized(uint8_t* p, bool device) {
   PCONV_CHECK(p != nullptr || sizes_.empty(), "BatchEngine::download_sized: null destination");
-  uint8_t* d = p;
-  for (size_t b = 0; b < sizes_.size(); ++b) {
-    const int64_t rb = dims_host_[b].row_bytes, rows = dims_host_[b].height;
-    const uint8_t* s = frame_at(cur_) + static_cast<int64_t>(b) * stride_;  // the newest frames
-    if (opt_.kernel_copies)
-      launch_copy_rows(s, lay_.pitch, d, rb, rb, rows, cs_);
-    else
-      PCONV_HIP_CHECK(hipMemcpy2DAsync(d, rb, s, lay_.pitch, rb, rows,
-                                       device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, cs_));
-    d += rb * rows;
+  copy_images(false, p, static_cast<int>(dims_host_.size()), dims_host_.data(), device);
+}
+
+// What every launch over images [0, n) of the current frames shares: whole
+// images, the extents table in mixed mode, the table of open images while a
+// compacting run_until_stable has retired some.
+StencilLaunch BatchEngine::base_launch(int n) const {
+  StencilLaunch a;
+  a.src = frame_at(cur_);
+  a.pitch = lay_.pitch;
+  a.row_bytes = lay_.row_bytes;
+  a.r0 = 0;
+  a.r1 = lay_.rows;
+  a.frame_lo = -lay_.halo;
+  a.frame_hi = lay_.rows + lay_.halo;
+  a.g_row0 = 0;
+  a.height = geom_.height;
+  a.border = opt_.border;
+  a.images.frames = n;
+  a.images.stride = stride_;
+  if (!sizes_.empty()) {
+    a.images.dims = reinterpret_cast<const ImageDims*>(dims_.dev.data());
+    a.images.dims_host = dims_host_.data();
   }
+  if (!active_host_.empty()) {
+    a.images.active = reinterpret_cast<const int32_t*>(active_.dev.data());
+    a.images.active_host = active_host_.data();
+    a.images.count = static_cast<int>(active_host_.size());
+  }
+  return a;
 }
 
 void BatchEngine::run(int reps, int n) {
@@ -218,26 +208,14 @@ void BatchEngine::run(int reps, int n) {
     // a capturing stream.
     for (const auto& p : ph) {
       for (const auto& l : p.launches) {
-        StencilLaunch a;
-        a.src = frame_at(cur_);
+        StencilLaunch a = base_launch(n);
         a.dst = frame_at(cur_ ^ 1);
-        a.pitch = lay_.pitch;
-        a.row_bytes = lay_.row_bytes;
         a.r0 = l.lo;
         a.r1 = l.hi;
-        a.frame_lo = -lay_.halo;
-        a.frame_hi = lay_.rows + lay_.halo;
         a.steps = l.steps;
-        a.g_row0 = 0;
-        a.height = geom_.height;
-        a.border = opt_.border;
-        a.batch = n;
-        a.batch_stride = stride_;
-        set_dims(a);
-        set_active(a);
         launch_stencil(filter_, geom_.channels, a, cs_, opt_.variant);
         ++stats_.launches;
-        stats_.image_launches += a.batch;
+        stats_.image_launches += a.images.images();
       }
       cur_ ^= 1;
     }
@@ -251,38 +229,18 @@ void BatchEngine::run(int reps, int n) {
 // ---- fixed points (BandEngine's pattern, one counter per image) -----------
 
 void BatchEngine::launch_batch_residual(int n) {
-  StencilLaunch a;
-  a.src = frame_at(cur_);
-  a.pitch = lay_.pitch;
-  a.row_bytes = lay_.row_bytes;
-  a.r0 = 0;
-  a.r1 = lay_.rows;
-  a.frame_lo = -lay_.halo;
-  a.frame_hi = lay_.rows + lay_.halo;
-  a.g_row0 = 0;
-  a.height = geom_.height;
-  a.border = opt_.border;
-  a.batch = n;
-  a.batch_stride = stride_;
-  set_dims(a);
-  set_active(a);
-  launch_residual(filter_, geom_.channels, a, reinterpret_cast<uint64_t*>(res_count_.data()), cs_);
+  launch_residual(filter_, geom_.channels, base_launch(n), reinterpret_cast<uint64_t*>(res_count_.data()), cs_);
 }
 
 void BatchEngine::enqueue_residual(int n) {
   TraceRange tr("pconv.batch.residual");
   // The host waits for the counts: a check has no place in a graph.
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  PCONV_CHECK(hipStreamIsCapturing(cs_, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone,
-              "BatchEngine: a residual check cannot be enqueued on a capturing stream");
+  PCONV_CHECK(!stream_capturing(cs_), "BatchEngine: a residual check cannot be enqueued on a capturing stream");
   const size_t bytes = round_up<size_t>(sizeof(uint64_t) * static_cast<size_t>(capacity_), 16);
   if (!res_count_.data()) {
     res_count_ = DeviceBuffer(bytes);
     res_host_ = PinnedBuffer(bytes);
-    if (opt_.kernel_copies)
-      launch_fill_zero(res_count_.data(), static_cast<int64_t>(bytes), cs_);
-    else
-      PCONV_HIP_CHECK(hipMemsetAsync(res_count_.data(), 0, bytes, cs_));
+    zero_words(res_count_.data(), bytes);
     res_ev_ = Event::create();
     res_seen_.assign(static_cast<size_t>(capacity_), 0);
   }
@@ -291,11 +249,7 @@ void BatchEngine::enqueue_residual(int n) {
   // in order).  All `capacity` words are read back: those of images >= n have
   // not moved.
   launch_batch_residual(n);
-  if (opt_.kernel_copies)
-    launch_copy_rows(res_count_.data(), static_cast<int64_t>(bytes), res_host_.data(), static_cast<int64_t>(bytes),
-                     static_cast<int64_t>(bytes), 1, cs_);
-  else
-    PCONV_HIP_CHECK(hipMemcpyAsync(res_host_.data(), res_count_.data(), bytes, hipMemcpyDeviceToHost, cs_));
+  copy_words(res_host_.data(), res_count_.data(), bytes, hipMemcpyDeviceToHost);
   res_ev_.record(cs_);
 }
 

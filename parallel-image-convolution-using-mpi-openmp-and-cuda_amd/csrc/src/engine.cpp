@@ -231,8 +231,7 @@ void BandEngine::enqueue_phase(const Phase& p) {
     PCONV_CHECK(transport_ != nullptr, "band has neighbours but no halo transport is attached");
     hipStream_t ms = comm_stream();
     const bool split = ms != cs_;  // one stream: stream order is the dependency
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (split && hipStreamIsCapturing(cs_, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) {
+    if (split && stream_capturing(cs_)) {
       // Inside a graph capture the roles swap: the exchange stays on the
       // capturing stream and the INTERIOR launch goes to the forked one.
       // torch's bundled HIP 7.0 runtime recurses without end (stack overflow

@@ -405,37 +405,41 @@ PYBIND11_MODULE(_pconv_native, m) {
                                {static_cast<py::ssize_t>(b.size())}, {1});
       });
 
-  // Mixed sizes (StencilLaunch::dims): `dims` is the host copy as a list of
-  // (row_bytes, height) pairs, `dims_ptr` the device table's address.
-  // With an active-image table (set_active first) the list is indexed by frame
-  // and holds `batch_frames` pairs.
-  static const auto set_dims = [](StencilLaunch& a, std::vector<ImageDims>& host, const py::object& dims,
-                                  uintptr_t dims_ptr) {
-    if (!dims.is_none()) {
-      for (const auto& d : dims.cast<std::vector<std::pair<int32_t, int32_t>>>())
-        host.push_back(ImageDims{d.first, d.second});
-      if (a.active_host)
-        PCONV_CHECK(static_cast<int64_t>(host.size()) == a.batch_frames,
-                    "dims: with an active table the list must hold `batch_frames` (row_bytes, height) pairs");
-      else
-        PCONV_CHECK(static_cast<int64_t>(host.size()) == a.batch,
-                    "dims: the list must hold `batch` (row_bytes, height) pairs");
-      a.dims_host = host.data();
+  // StencilLaunch::images from the launch bindings' keyword arguments; the
+  // vectors hold the tables' host copies for the duration of the call.
+  //   batch / batch_stride: the images of the grid and the bytes between
+  // frames.  active / active_ptr: the table of open images, as a list of
+  // `batch` frame indices (the host copy) and the device table's address; the
+  // frames at the stride then number `batch_frames`, without a table `batch`.
+  //   dims / dims_ptr: the extents as a list of one (row_bytes, height) pair per
+  // FRAME (the host copy) and the device table's address.
+  struct ImageSetArgs {
+    std::vector<int32_t> active_host;
+    std::vector<ImageDims> dims_host;
+    void fill(ImageSet& s, int batch, int64_t batch_stride, const py::object& dims, uintptr_t dims_ptr,
+              const py::object& active = py::none(), uintptr_t active_ptr = 0, int batch_frames = 1) {
+      const bool table = !active.is_none() || active_ptr != 0;
+      s.frames = table ? batch_frames : batch;
+      s.stride = batch_stride;
+      s.count = table ? batch : 0;
+      if (!active.is_none()) {
+        active_host = active.cast<std::vector<int32_t>>();
+        PCONV_CHECK(static_cast<int64_t>(active_host.size()) == batch,
+                    "active: the list must hold `batch` frame indices");
+        s.active_host = active_host.data();
+      }
+      s.active = reinterpret_cast<const int32_t*>(active_ptr);
+      if (!dims.is_none()) {
+        for (const auto& d : dims.cast<std::vector<std::pair<int32_t, int32_t>>>())
+          dims_host.push_back(ImageDims{d.first, d.second});
+        PCONV_CHECK(static_cast<int64_t>(dims_host.size()) == (s.active_host ? batch_frames : batch),
+                    s.active_host
+                        ? "dims: with an active table the list must hold `batch_frames` (row_bytes, height) pairs"
+                        : "dims: the list must hold `batch` (row_bytes, height) pairs");
+        s.dims_host = dims_host.data();
+      }
+      s.dims = reinterpret_cast<const ImageDims*>(dims_ptr);
     }
-    a.dims = reinterpret_cast<const ImageDims*>(dims_ptr);
-  };
-  // Active images (StencilLaunch::active): `active` is the host copy as a list
-  // of frame indices (`batch` of them), `active_ptr` the device table's
-  // address, `batch_frames` the number of frames at the stride.
-  static const auto set_active = [](StencilLaunch& a, std::vector<int32_t>& host, const py::object& active,
-                                    uintptr_t active_ptr, int batch_frames) {
-    if (!active.is_none()) {
-      host = active.cast<std::vector<int32_t>>();
-      PCONV_CHECK(static_cast<int64_t>(host.size()) == a.batch, "active: the list must hold `batch` frame indices");
-      a.active_host = host.data();
-    }
-    a.active = reinterpret_cast<const int32_t*>(active_ptr);
-    a.batch_frames = batch_frames;
   };
   m.def(
       "launch_stencil",
@@ -444,13 +448,9 @@ PYBIND11_MODULE(_pconv_native, m) {
          uintptr_t stream, const std::string& variant, const std::string& border, int batch, int64_t batch_stride,
          py::object dims, uintptr_t dims_ptr, py::object active, uintptr_t active_ptr, int batch_frames) {
         StencilLaunch a;
-        std::vector<ImageDims> dims_host;
-        std::vector<int32_t> active_host;
+        ImageSetArgs images;
         a.border = parse_border(border);
-        a.batch = batch;
-        a.batch_stride = batch_stride;
-        set_active(a, active_host, active, active_ptr, batch_frames);
-        set_dims(a, dims_host, dims, dims_ptr);
+        images.fill(a.images, batch, batch_stride, dims, dims_ptr, active, active_ptr, batch_frames);
         a.src = reinterpret_cast<const uint8_t*>(src);
         a.dst = reinterpret_cast<uint8_t*>(dst);
         a.pitch = pitch;
@@ -477,8 +477,8 @@ PYBIND11_MODULE(_pconv_native, m) {
          int64_t r1, int64_t frame_lo, int64_t frame_hi, int64_t g_row0, int64_t height, uintptr_t stream,
          const std::string& border, py::object dims, uintptr_t dims_ptr) {
         StencilLaunch a;
-        std::vector<ImageDims> dims_host;
-        set_dims(a, dims_host, dims, dims_ptr);
+        ImageSetArgs images;
+        images.fill(a.images, 1, 0, dims, dims_ptr);
         a.border = parse_border(border);
         a.src = reinterpret_cast<const uint8_t*>(src);
         a.pitch = pitch;
@@ -514,13 +514,9 @@ PYBIND11_MODULE(_pconv_native, m) {
          int64_t g_row0, int64_t height, uintptr_t stream, const std::string& border, py::object dims,
          uintptr_t dims_ptr, py::object active, uintptr_t active_ptr, int batch_frames) {
         StencilLaunch a;
-        std::vector<ImageDims> dims_host;
-        std::vector<int32_t> active_host;
+        ImageSetArgs images;
         a.border = parse_border(border);
-        a.batch = batch;
-        a.batch_stride = batch_stride;
-        set_active(a, active_host, active, active_ptr, batch_frames);
-        set_dims(a, dims_host, dims, dims_ptr);
+        images.fill(a.images, batch, batch_stride, dims, dims_ptr, active, active_ptr, batch_frames);
         a.src = reinterpret_cast<const uint8_t*>(src);
         a.pitch = pitch;
         a.row_bytes = row_bytes;

@@ -63,6 +63,21 @@ _CPU_CHECK_EVERY = 32
 _GPU_CHECK_LAUNCHES = 16
 
 
+def _check_stable_args(max_reps, check_every):
+    """The argument checks every run to the fixed point shares:
+    ``(int(max_reps), int(check_every) or None for the caller's default)``."""
+    if max_reps < 0:
+        raise ValueError("max_reps must be >= 0")
+    if check_every is not None and int(check_every) < 1:
+        raise ValueError("check_every must be >= 1")
+    return int(max_reps), None if check_every is None else int(check_every)
+
+
+def _stable_info(st) -> StableInfo:
+    """The native engines' (reps_done, converged, residual, checks)."""
+    return StableInfo(int(st[0]), bool(st[1]), int(st[2]), int(st[3]))
+
+
 class Engine:
     """Persistent single-GPU convolution engine for one image geometry.
 
@@ -160,13 +175,11 @@ class Engine:
         """Repetitions in chunks of ``check_every`` (default 16 x fuse) with a
         residual check after each, stopping at the first fixed point or at
         ``max_reps``; returns ``(image, StableInfo)``."""
-        if max_reps < 0:
-            raise ValueError("max_reps must be >= 0")
-        k = _GPU_CHECK_LAUNCHES * self.fuse if check_every is None else int(check_every)
-        if k < 1:
-            raise ValueError("check_every must be >= 1")
-        out, st = self._with_frame(img, lambda: self._eng.run_until_stable(int(max_reps), k))
-        return out, StableInfo(int(st[0]), bool(st[1]), int(st[2]), int(st[3]))
+        max_reps, k = _check_stable_args(max_reps, check_every)
+        if k is None:
+            k = _GPU_CHECK_LAUNCHES * self.fuse
+        out, st = self._with_frame(img, lambda: self._eng.run_until_stable(max_reps, k))
+        return out, _stable_info(st)
 
 
 _ENGINES: "OrderedDict[tuple, Engine]" = OrderedDict()
@@ -282,10 +295,7 @@ def convolve_until_stable(image, max_reps: int, filter="gaussian", check_every: 
     repetition returns the same bytes, so a converged result equals
     ``convolve(image, max_reps, ...)``.  Returns ``(out, StableInfo)``.
     """
-    if max_reps < 0:
-        raise ValueError("max_reps must be >= 0")
-    if check_every is not None and int(check_every) < 1:
-        raise ValueError("check_every must be >= 1")
+    _check_stable_args(max_reps, check_every)
     flt = get_filter(filter)
     check_border(border)
     is_tensor = isinstance(image, torch.Tensor)
@@ -375,64 +385,77 @@ class BatchEngine:
             raise ValueError(f"{shape[0]} images exceed the engine's capacity {self.capacity}")
         return shape[0]
 
-    def _with_frames_numpy(self, stack: np.ndarray, work):
-        """Upload the stack, ``work(n)`` on the resident frames, download the
-        newest frames: ``(out, work's result)`` (``None`` for an empty stack)."""
-        src = np.ascontiguousarray(stack, dtype=np.uint8)
-        n = self._n = self._check_stack(src.shape)
-        out = np.empty_like(src)
+    def _transfer(self, flat, n: int, work, sizes=None):
+        """The bracket every call shares.  ``flat``: the packed bytes of ``n``
+        images, a 1-D NumPy array or CUDA tensor (which never leaves the
+        device); ``sizes``: their ``[(width, height)]``, or ``None`` for images
+        of the engine's geometry.  Waits for the caller's stream, uploads,
+        ``work(n)`` on the resident frames, downloads the newest frames in the
+        same packing, signals the caller's stream (host memory: synchronises):
+        ``(out, work's result)``, ``(out, None)`` for no images."""
+        e = self._eng
+        self._n = n
+        device = isinstance(flat, torch.Tensor)
+        out = torch.empty_like(flat) if device else np.empty_like(flat)
         if n == 0:
             return out, None
-        self._eng.upload(src.reshape(-1), n)
+        form = ("" if sizes is None else "_sized") + ("_ptr" if device else "")
+        kw = {"device": True} if device else {}
+        if device:
+            ts = torch.cuda.current_stream(flat.device).cuda_stream
+            e.wait_stream(ts)
+        getattr(e, "upload" + form)(flat.data_ptr() if device else flat, n if sizes is None else sizes, **kw)
         res = work(n)
-        self._eng.download(out.reshape(-1), n)
-        self._eng.synchronize()
-        return out, res
-
-    def _with_frames_tensor(self, stack: torch.Tensor, work):
-        if stack.device.type != "cuda":
-            out, res = self._with_frames_numpy(stack.numpy(), work)
-            return torch.from_numpy(out), res
-        src = stack.contiguous()
-        n = self._n = self._check_stack(src.shape)
-        out = torch.empty_like(src)
-        if n == 0:
-            return out, None
-        ts = torch.cuda.current_stream(src.device).cuda_stream
-        self._eng.wait_stream(ts)
-        self._eng.upload_ptr(src.data_ptr(), n, device=True)
-        res = work(n)
-        self._eng.download_ptr(out.data_ptr(), n, device=True)
-        self._eng.signal_stream(ts)
-        src.record_stream(torch.cuda.current_stream(src.device))
+        getattr(e, "download" + form)(out.data_ptr() if device else out, *([n] if sizes is None else []), **kw)
+        if device:
+            e.signal_stream(ts)
+            flat.record_stream(torch.cuda.current_stream(flat.device))
+        else:
+            e.synchronize()
         return out, res
 
     def _with_frames(self, stack, work):
-        if isinstance(stack, torch.Tensor):
-            return self._with_frames_tensor(stack, work)
-        return self._with_frames_numpy(np.asarray(stack), work)
+        """:meth:`_transfer` of a stack: ``(out stack in the input's container,
+        work's result)``."""
+        is_tensor = isinstance(stack, torch.Tensor)
+        on_gpu = is_tensor and stack.device.type == "cuda"
+        src = stack.contiguous() if on_gpu else np.ascontiguousarray(stack.numpy() if is_tensor else stack,
+                                                                     dtype=np.uint8)
+        out, res = self._transfer(src.reshape(-1), self._check_stack(src.shape), work)
+        out = out.reshape(src.shape)
+        return (torch.from_numpy(out) if is_tensor and not on_gpu else out), res
 
     def run_numpy(self, stack: np.ndarray, reps: int) -> np.ndarray:
-        return self._with_frames_numpy(stack, lambda n: self._eng.run(int(reps), n))[0]
+        return self._with_frames(np.asarray(stack), lambda n: self._eng.run(int(reps), n))[0]
 
     def run_tensor(self, stack: torch.Tensor, reps: int) -> torch.Tensor:
-        return self._with_frames_tensor(stack, lambda n: self._eng.run(int(reps), n))[0]
+        return self._with_frames(stack, lambda n: self._eng.run(int(reps), n))[0]
 
     def __call__(self, stack, reps: int):
         if isinstance(stack, torch.Tensor):
             return self.run_tensor(stack, reps)
-        return self.run_numpy(np.asarray(stack), reps)
+        return self.run_numpy(stack, reps)
 
     # ---- fixed points ------------------------------------------------
+    def _residual(self, images, bracket) -> np.ndarray:
+        if images is None:
+            res = self._eng.residual(self._n) if self._n else []
+        else:
+            res = bracket(images, self._eng.residual)[1] or []
+        return np.asarray(res, dtype=np.int64).reshape(-1)
+
+    def _until_stable(self, images, bracket, max_reps, check_every, compact):
+        max_reps, k = _check_stable_args(max_reps, check_every)
+        if k is None:
+            k = _GPU_CHECK_LAUNCHES * self.fuse
+        out, st = bracket(images, lambda n: self._eng.run_until_stable(max_reps, k, n, bool(compact)))
+        return out, [_stable_info(s) for s in (st or [])]
+
     def residual(self, stack=None) -> np.ndarray:
         """Per image, the bytes one more repetition would change, ``(n,)``
         int64 from one launch: of the images of ``stack``, or (``None``) of the
         frames the engine holds after its last call, for that call's ``n``."""
-        if stack is None:
-            res = self._eng.residual(self._n) if self._n else []
-        else:
-            res = self._with_frames(stack, self._eng.residual)[1] or []
-        return np.asarray(res, dtype=np.int64).reshape(-1)
+        return self._residual(stack, self._with_frames)
 
     def run_until_stable(self, stack, max_reps: int, check_every: Optional[int] = None, compact: bool = False):
         """All images of ``stack`` in chunks of ``check_every`` repetitions
@@ -446,19 +469,11 @@ class BatchEngine:
         launches that follow the chunk already in flight; the return values are
         identical, ``stats.image_launches`` shows the work saved.  Retired
         launches run the latency model's tile (no first-use tuning)."""
-        if max_reps < 0:
-            raise ValueError("max_reps must be >= 0")
-        k = _GPU_CHECK_LAUNCHES * self.fuse if check_every is None else int(check_every)
-        if k < 1:
-            raise ValueError("check_every must be >= 1")
-        out, st = self._with_frames(stack, lambda n: self._eng.run_until_stable(int(max_reps), k, n, bool(compact)))
-        return out, [StableInfo(int(s[0]), bool(s[1]), int(s[2]), int(s[3])) for s in (st or [])]
-
+        return self._until_stable(stack, self._with_frames, max_reps, check_every, compact)
 
     # ---- mixed sizes ---------------------------------------------------
     def _check_images(self, images):
-        """The images as a list, their (width, height) list and whether they
-        are tensors (all of one kind, checked by the caller for the API)."""
+        """The images as a list and their (width, height) list."""
         seq = list(images)
         if len(seq) > self.capacity:
             raise ValueError(f"{len(seq)} images exceed the engine's capacity {self.capacity}")
@@ -472,39 +487,24 @@ class BatchEngine:
         return seq, sizes
 
     def _with_images(self, images, work):
-        """Upload the images top-left into their frames, ``work(n)`` on them,
-        download each image's region: ``([out], work's result)``."""
+        """:meth:`_transfer` of a sequence of images of any sizes within the
+        envelope, each top-left in its frame: ``([out], work's result)``, every
+        output in its input's container."""
         seq, sizes = self._check_images(images)
-        n = self._n = len(seq)
-        if n == 0:
-            return [], None
         tensors = [isinstance(im, torch.Tensor) for im in seq]
-        if all(tensors) and all(im.device.type == "cuda" for im in seq):
+        on_gpu = bool(seq) and all(tensors) and all(im.device.type == "cuda" for im in seq)
+        if on_gpu:
             flat = torch.cat([im.contiguous().reshape(-1) for im in seq])
-            out = torch.empty_like(flat)
-            ts = torch.cuda.current_stream(flat.device).cuda_stream
-            self._eng.wait_stream(ts)
-            self._eng.upload_sized_ptr(flat.data_ptr(), sizes, device=True)
-            res = work(n)
-            self._eng.download_sized_ptr(out.data_ptr(), device=True)
-            self._eng.signal_stream(ts)
-            flat.record_stream(torch.cuda.current_stream(flat.device))
-            wrap = lambda a: a  # noqa: E731
         else:
-            arrs = [np.ascontiguousarray(im.cpu().numpy() if t else im, dtype=np.uint8) for im, t in zip(seq, tensors)]
-            flat = np.concatenate([a.reshape(-1) for a in arrs])
-            out = np.empty_like(flat)
-            self._eng.upload_sized(flat, sizes)
-            res = work(n)
-            self._eng.download_sized(out)
-            self._eng.synchronize()
-            wrap = None
+            flat = np.concatenate([np.ascontiguousarray(im.cpu().numpy() if t else im, dtype=np.uint8).reshape(-1)
+                                   for im, t in zip(seq, tensors)] or [np.empty(0, np.uint8)])
+        out, res = self._transfer(flat, len(seq), work, sizes)
         outs, at = [], 0
         for im, t in zip(seq, tensors):
             k = int(np.prod(tuple(im.shape)))
             piece = out[at:at + k].reshape(tuple(im.shape))
             at += k
-            if wrap is None:
+            if not on_gpu:
                 piece = torch.from_numpy(piece.copy()) if t else piece.copy()
             outs.append(piece)
         return outs, res
@@ -518,24 +518,14 @@ class BatchEngine:
     def residual_images(self, images=None) -> np.ndarray:
         """:meth:`residual` for mixed sizes: of ``images``, or (``None``) of the
         frames the engine holds after its last mixed-size call."""
-        if images is None:
-            res = self._eng.residual(self._n) if self._n else []
-        else:
-            res = self._with_images(images, self._eng.residual)[1] or []
-        return np.asarray(res, dtype=np.int64).reshape(-1)
+        return self._residual(images, self._with_images)
 
     def run_images_until_stable(self, images, max_reps: int, check_every: Optional[int] = None,
                                 compact: bool = False):
         """:meth:`run_until_stable` for mixed sizes: ``([out], [StableInfo])``,
         entry b what a single-image run of image b returns (``compact`` as
         there: same return values, converged images leave the launches)."""
-        if max_reps < 0:
-            raise ValueError("max_reps must be >= 0")
-        k = _GPU_CHECK_LAUNCHES * self.fuse if check_every is None else int(check_every)
-        if k < 1:
-            raise ValueError("check_every must be >= 1")
-        outs, st = self._with_images(images, lambda n: self._eng.run_until_stable(int(max_reps), k, n, bool(compact)))
-        return outs, [StableInfo(int(s[0]), bool(s[1]), int(s[2]), int(s[3])) for s in (st or [])]
+        return self._until_stable(images, self._with_images, max_reps, check_every, compact)
 
 
 # convolve_batch's own engine cache (the single-image engines keep theirs).
@@ -694,10 +684,7 @@ def convolve_batch_until_stable(images, max_reps: int, filter="gaussian", check_
     image and already stop each image at its own fixed point.  The return
     values are identical for both settings on every backend.
     """
-    if max_reps < 0:
-        raise ValueError("max_reps must be >= 0")
-    if check_every is not None and int(check_every) < 1:
-        raise ValueError("check_every must be >= 1")
+    _check_stable_args(max_reps, check_every)
     flt, stack, is_tensor, geo, backend = _prepare_batch(images, filter, backend, border, batch_size)
     n_img = int(stack.shape[0])
     if n_img == 0:
@@ -883,10 +870,7 @@ def convolve_many_until_stable(images, max_reps: int, filter="gaussian", check_e
     ``compact`` is :func:`convolve_batch_until_stable`'s, per bucket: same
     return values; the ``cpu`` and ``numpy`` backends accept and ignore it
     (they already stop each image at its own fixed point)."""
-    if max_reps < 0:
-        raise ValueError("max_reps must be >= 0")
-    if check_every is not None and int(check_every) < 1:
-        raise ValueError("check_every must be >= 1")
+    _check_stable_args(max_reps, check_every)
     flt, seq, is_tensor, ch, backend = _prepare_many(images, filter, backend, border, batch_size, min_fill)
     if not seq:
         return [], []

@@ -1,7 +1,7 @@
-// Native unit tests for the host side of mixed-size batches (no GPU, no HIP
+// Native unit tests for the host side of a launch's image set (no GPU, no HIP
 // calls): the extents table BatchEngine::upload_sized builds, the packed
-// buffer's size, the launch guards of StencilLaunch::dims and the tuners'
-// live-workgroup count.  Built by `make -C <pkg>/csrc test-native` with
+// buffer's size, the launch guards of StencilLaunch::images and their order,
+// the kernels' image-set arguments and the tuners' live-workgroup count.  Built by `make -C <pkg>/csrc test-native` with
 // AddressSanitizer + UndefinedBehaviorSanitizer next to test_native.cpp.
 #include <cstdio>
 #include <functional>
@@ -10,7 +10,7 @@
 
 #include "pconv/batch_engine.hpp"
 #include "pconv/kernels.hpp"
-#include "tuning.hpp"
+#include "image_set.hpp"
 
 using namespace pconv;
 
@@ -67,10 +67,23 @@ StencilLaunch envelope(const std::vector<ImageDims>& host) {
   a.steps = 8;
   a.g_row0 = 0;
   a.height = 61;
-  a.batch = static_cast<int>(host.size());
-  a.batch_stride = 384 * 77;
-  a.dims = device_table;
-  a.dims_host = host.data();
+  a.images.frames = static_cast<int>(host.size());
+  a.images.stride = 384 * 77;
+  a.images.dims = device_table;
+  a.images.dims_host = host.data();
+  return a;
+}
+
+// The envelope's frames without extents, `table` naming the grid's images.
+StencilLaunch with_table(int frames, const std::vector<int32_t>& table) {
+  static const int32_t device_table[8] = {};  // only its address is looked at
+  StencilLaunch a = envelope({});
+  a.images.frames = frames;
+  a.images.dims = nullptr;
+  a.images.dims_host = nullptr;
+  a.images.active = device_table;
+  a.images.active_host = table.data();
+  a.images.count = static_cast<int>(table.size());
   return a;
 }
 
@@ -82,10 +95,10 @@ void test_guards() {
   EXPECT(thrown([&] { check_dims("t", none, 3); }).empty());
   {
     StencilLaunch b = a;
-    b.dims_host = nullptr;
+    b.images.dims_host = nullptr;
     EXPECT(has(thrown([&] { check_dims("t", b, 3); }), "given together"));
     b = a;
-    b.dims = nullptr;
+    b.images.dims = nullptr;
     EXPECT(has(thrown([&] { check_dims("t", b, 3); }), "given together"));
   }
   for (int k = 0; k < 3; ++k) {
@@ -105,6 +118,98 @@ void test_guards() {
   }
 }
 
+void test_active_guards() {
+  const std::vector<int32_t> good = {1, 3};
+  const StencilLaunch a = with_table(4, good);
+  EXPECT(thrown([&] { check_active("t", a); }).empty());
+  EXPECT(thrown([&] { check_image_set("t", a, 3); }).empty());
+  EXPECT(a.images.has_table() && a.images.images() == 2 && a.images.frame_of(0) == 1 && a.images.frame_of(1) == 3);
+  StencilLaunch none;  // no table at all: nothing to check, image k is frame k
+  EXPECT(thrown([&] { check_active("t", none); }).empty());
+  EXPECT(!none.images.has_table() && none.images.images() == 1 && none.images.frame_of(0) == 0 && none.images.single());
+  {
+    StencilLaunch b = a;
+    b.images.active_host = nullptr;
+    EXPECT(has(thrown([&] { check_active("t", b); }), "t: active and active_host must be given together"));
+    b = a;
+    b.images.active = nullptr;
+    EXPECT(has(thrown([&] { check_active("t", b); }), "t: active and active_host must be given together"));
+  }
+  {
+    const StencilLaunch b = with_table(1, good);
+    EXPECT(has(thrown([&] { check_active("t", b); }), "t: active holds 2 entries, more than batch_frames 1"));
+    StencilLaunch e = a;  // a table of no entries
+    e.images.count = 0;
+    EXPECT(has(thrown([&] { check_active("t", e); }), "t: active needs batch >= 1 entries"));
+    EXPECT(has(thrown([&] { check_image_set("t", e, 3); }), "t: batch must be >= 1"));
+  }
+  {
+    const std::vector<int32_t> neg = {-1, 2}, big = {1, 4};
+    EXPECT(has(thrown([&] { check_active("t", with_table(4, neg)); }), "t: active[0] = -1 is outside [0, batch_frames 4)"));
+    EXPECT(has(thrown([&] { check_active("t", with_table(4, big)); }), "t: active[1] = 4 is outside [0, batch_frames 4)"));
+    const std::vector<int32_t> equal = {1, 1}, down = {2, 0};
+    EXPECT(has(thrown([&] { check_active("t", with_table(4, equal)); }),
+               "t: active[1] = 1 does not exceed the entry before it (the table must be strictly increasing)"));
+    EXPECT(has(thrown([&] { check_active("t", with_table(4, down)); }),
+               "t: active[1] = 0 does not exceed the entry before it (the table must be strictly increasing)"));
+  }
+  {
+    // the stride rules are the FRAMES': 4 frames, whatever the single entry
+    const std::vector<int32_t> one = {3};
+    StencilLaunch b = with_table(4, one);
+    EXPECT(thrown([&] { check_image_set("t", b, 3); }).empty());
+    b.images.stride = 384 * 77 + 8;
+    EXPECT(has(thrown([&] { check_image_set("t", b, 3); }), "t: batch_stride must be a multiple of 16"));
+    b.images.stride = 384 * 77 - 16;
+    EXPECT(has(thrown([&] { check_image_set("t", b, 3); }), "is smaller than a frame (29568 bytes): frames would overlap"));
+    b.images.frames = 1;  // one frame has no stride to obey, but the table no longer fits
+    EXPECT(has(thrown([&] { check_image_set("t", b, 3); }), "t: active[0] = 3 is outside [0, batch_frames 1)"));
+  }
+}
+
+// check_image_set reports the frames first, then the table, then the extents.
+void test_guard_order() {
+  const std::vector<ImageDims> bad_dims = {{231, 61}, {2, 1}, {231, 61}, {231, 61}};
+  const std::vector<int32_t> bad_table = {2, 2};
+  static const int32_t device_table[8] = {};
+  StencilLaunch a = envelope(bad_dims);
+  a.images.active = device_table;
+  a.images.active_host = bad_table.data();
+  a.images.count = 2;
+  a.images.stride = 384 * 77 + 8;
+  EXPECT(has(thrown([&] { check_image_set("t", a, 3); }), "multiple of 16"));  // all three are wrong
+  a.images.stride = 384 * 77;
+  EXPECT(has(thrown([&] { check_image_set("t", a, 3); }), "active[1] = 2 does not exceed"));
+  const std::vector<int32_t> table = {0, 2};  // the bad extent is frame 1's: checked although no grid slot names it
+  a.images.active_host = table.data();
+  EXPECT(has(thrown([&] { check_image_set("t", a, 3); }), "dims[1].row_bytes"));
+  const std::vector<ImageDims> good_dims = {{231, 61}, {3, 1}, {231, 61}, {231, 61}};
+  a.images.dims_host = good_dims.data();
+  EXPECT(thrown([&] { check_image_set("t", a, 3); }).empty());
+  // "not supported by kernel": the first present feature of the list
+  EXPECT(has(thrown([&] { check_temporal_only("t", "int9", {{"active", false}, {"dims", true}, {"batch", true}}); }),
+             "t: dims not supported by kernel 'int9' (temporal and float_temporal only)"));
+  EXPECT(thrown([&] { check_temporal_only("t", "int9", {{"active", false}, {"dims", false}}); }).empty());
+}
+
+void test_batch_kernel_args() {
+  StencilLaunch lone;  // stride 0 whatever the field holds: the kernels add nothing to the base pointers
+  lone.images.stride = 4096;
+  BatchKernelArgs k = batch_kernel_args(lone);
+  EXPECT(k.stride == 0 && k.dims == nullptr && k.active == nullptr && k.last_frame == 0u);
+  const std::vector<ImageDims> three = {{231, 61}, {3, 1}, {120, 61}};
+  const StencilLaunch batch = envelope(three);
+  k = batch_kernel_args(batch);
+  EXPECT(k.stride == 384 * 77 && k.dims == batch.images.dims && k.active == nullptr && k.last_frame == 0u);
+  const std::vector<int32_t> table = {1, 3};
+  const StencilLaunch some = with_table(4, table);
+  k = batch_kernel_args(some);
+  EXPECT(k.stride == 384 * 77 && k.dims == nullptr && k.active == some.images.active && k.last_frame == 3u);
+  const std::vector<int32_t> one = {0};  // a table over ONE frame keeps the stride too
+  k = batch_kernel_args(with_table(1, one));
+  EXPECT(k.stride == 384 * 77 && k.last_frame == 0u);
+}
+
 void test_live_workgroups() {
   // tile {4, 8, 8} at 8 steps, RGB: 208 x 48 bytes x rows of output, strips in pairs
   const std::vector<ImageDims> host = {{231, 61}, {3, 1}, {208, 48}, {209, 49}};
@@ -116,6 +221,17 @@ void test_live_workgroups() {
   StencilLaunch none;
   EXPECT(live_workgroups(none, 208, 48, 2) == 0);
   EXPECT(live_workgroups(a, 0, 48, 2) == 0);
+  // with a table only the frames it names count, and dims stays indexed by frame
+  const std::vector<int32_t> table = {1, 3};
+  static const int32_t device_table[8] = {};
+  StencilLaunch t = a;
+  t.images.active = device_table;
+  t.images.active_host = table.data();
+  t.images.count = 2;
+  EXPECT(t.images.dims_entries() == 4 && t.images.images() == 2);
+  EXPECT(thrown([&] { check_image_set("t", t, 1); }).empty());
+  EXPECT(live_workgroups(t, 208, 48, 2) == 1 + 2);
+  EXPECT(live_workgroups(t, 208, 48, 1) == 1 + 4);
 }
 
 }  // namespace
@@ -123,6 +239,9 @@ void test_live_workgroups() {
 int main() {
   test_dims_table();
   test_guards();
+  test_active_guards();
+  test_guard_order();
+  test_batch_kernel_args();
   test_live_workgroups();
   std::printf("ragged native tests: %d checks, %d failures\n", g_checks, g_failures);
   return g_failures ? 1 : 0;

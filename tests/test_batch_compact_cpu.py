@@ -8,6 +8,7 @@ Exact integers and exact bytes only."""
 import numpy as np
 import pytest
 
+import batch_modes_recipe as modes
 from batch_compact_formula import chunk_launches, converged_at, expected_image_launches
 from batch_converge_recipe import BORDERS, GEOMS, check_spread, oracle, recipe
 
@@ -90,3 +91,31 @@ def test_formula_on_the_recipe(pconv_mod, c, h, w, filt, border):
         on, launches = expected_image_launches(400, 8, fuse, converged_at(infos), True)
         off, _ = expected_image_launches(400, 8, fuse, converged_at(infos), False)
         assert off == launches * len(infos) and 0 < on < off
+
+
+@pytest.mark.parametrize("border", BORDERS)
+@pytest.mark.parametrize("c", modes.CHANNELS)
+def test_modes_recipe(pconv_mod, c, border):
+    """The three steps test_gpu_batch_compact.py takes one engine through, on
+    the oracle alone: the sizes fit the engine, the CPU backends agree on every
+    image, and every step has something to retire and something still open."""
+    plan = modes.steps(c, border)
+    assert [kind for kind, _ in plan] == ["images", "stack", "images"]
+    assert [(im.shape[1], im.shape[0]) for im in plan[0][1]] == [(67, 33), (5, 31), (64, 32), (1, 1)]
+    assert [(im.shape[1], im.shape[0]) for im in plan[1][1]] == [(modes.W, modes.H)] * 3
+    assert len({im.shape for im in plan[2][1]}) == 3 and {im.shape for im in plan[2][1]}.isdisjoint(
+        {im.shape for im in plan[0][1]})
+    flat = plan[1][1][1]
+    assert int(flat.min()) == int(flat.max())  # the stack's constant image
+    for (kind, imgs), (outs, infos) in zip(plan, modes.oracle(pconv_mod, c, border)):
+        assert 1 <= len(imgs) <= modes.CAPACITY
+        for im, out, info in zip(imgs, outs, infos):
+            assert im.dtype == np.uint8 and im.ndim == (2 if c == 1 else 3) and im.shape[:2] <= (modes.H, modes.W)
+            ro, ri = pconv_mod.convolve_until_stable(im, modes.MAX_REPS, modes.FILTER, check_every=modes.CHECK_EVERY,
+                                                     backend="numpy", border=border)
+            assert np.array_equal(out, ro) and info == ri
+        assert modes.retires(infos) and not all(i.converged for i in infos), (kind, infos)
+        on = expected_image_launches(modes.MAX_REPS, modes.CHECK_EVERY, modes.FUSE, converged_at(infos), True)
+        assert 0 < on[0] < on[1] * len(imgs)
+    if border == "replicate":
+        assert modes.oracle(pconv_mod, c, border)[1][1][1] == pconv_mod.StableInfo(modes.CHECK_EVERY, True, 0, 1)

@@ -13,6 +13,7 @@ Exact integers and exact bytes only.  Tuning is off, shapes are forced."""
 import numpy as np
 import pytest
 
+import batch_modes_recipe as modes
 from batch_compact_formula import converged_at, expected_image_launches
 from batch_converge_recipe import BORDERS, GEOMS, NAME, RUNS, check_spread, oracle, recipe
 
@@ -140,6 +141,32 @@ def test_run_images_until_stable_compact(pconv_mod, geom):
         assert stats == expected_image_launches(max_reps, k, 8, converged_at(infos), True), (geom, max_reps)
         offs, off_infos = eng.run_images_until_stable(imgs, max_reps, k)
         assert off_infos == infos and all(np.array_equal(a, b) for a, b in zip(outs, offs))
+
+
+@pytest.mark.parametrize("border", BORDERS)
+@pytest.mark.parametrize("c", modes.CHANNELS)
+def test_one_engine_through_mixed_plain_and_mixed_again(pconv_mod, c, border):
+    """The modes share the engine's staged tables and its per-image copies: one
+    engine runs mixed sizes, a plain stack and other mixed sizes in a row, every
+    run compacting, and each image ends as its single-image CPU run ends."""
+    eng = pconv_mod.BatchEngine(modes.W, modes.H, NAME[c], modes.CAPACITY, modes.FILTER, fuse=modes.FUSE, border=border)
+    assert eng.fuse == modes.FUSE
+    for step, ((kind, imgs), (refs, rinfos)) in enumerate(zip(modes.steps(c, border), modes.oracle(pconv_mod, c, border))):
+        case = (c, border, step)
+        if kind == "stack":
+            outs, infos = eng.run_until_stable(np.stack(imgs), modes.MAX_REPS, modes.CHECK_EVERY, compact=True)
+            held = eng.residual()
+        else:
+            outs, infos = eng.run_images_until_stable(imgs, modes.MAX_REPS, modes.CHECK_EVERY, compact=True)
+            held = eng.residual_images()
+        stats = (eng.stats.image_launches, eng.stats.launches)
+        assert infos == rinfos, case
+        assert len(outs) == len(refs) and all(np.array_equal(o, r) for o, r in zip(outs, refs)), case
+        assert held.tolist() == [i.residual for i in rinfos], case
+        assert stats == expected_image_launches(modes.MAX_REPS, modes.CHECK_EVERY, modes.FUSE, converged_at(infos),
+                                                True), case
+        if modes.retires(infos):
+            assert stats[0] < stats[1] * len(imgs), case
 
 
 @pytest.mark.parametrize("border", BORDERS)
