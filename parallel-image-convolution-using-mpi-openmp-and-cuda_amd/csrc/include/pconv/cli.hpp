@@ -28,6 +28,9 @@ struct CliConfig {
   int64_t width = 0, height = 0;
   int reps = 0;
   Channels channels = Channels::Grey;
+  // --depth 8|16: bits per sample; 16: little-endian unsigned samples, the
+  // gaussian on 1 GPU or the CPU backends (parse_cli names what it excludes).
+  int depth = 8;
 
   Backend backend = Backend::Hip;
   int gpus = 1;

@@ -35,7 +35,11 @@ enum class CpuBackend { Serial, OpenMP };
 // modified.
 void cpu_step(const Filter& f, Channels ch, const FrameLayout& lay, const uint8_t* src_frame,
               uint8_t* dst_frame, int64_t r0, int64_t r1, CpuBackend be, Border border = Border::Zero,
-              int64_t g_row0 = 0, int64_t height = -1);
+              int64_t g_row0 = 0, int64_t height = -1, int depth = 8);
+// depth 16 (cpu_step, cpu_fused_launch, HostFrames through its geometry): the
+// frame's rows hold unsigned 16-bit samples in host byte order (row_bytes =
+// width x channels x 2), out = (sum w p) >> 4 in 32-bit integers; the gaussian
+// only, any other filter is refused by name.
 
 // Reference semantics of one fused launch (what the temporal GPU kernel
 // computes): `steps` repetitions starting from src rows [lo-steps, hi+steps),
@@ -44,7 +48,7 @@ void cpu_step(const Filter& f, Channels ch, const FrameLayout& lay, const uint8_
 // there); writes rows [lo, hi) of dst only.  g_row0 = global row of frame row 0.
 void cpu_fused_launch(const Filter& f, Channels ch, const FrameLayout& lay, const uint8_t* src_frame,
                       uint8_t* dst_frame, int64_t lo, int64_t hi, int steps, int64_t g_row0, int64_t height,
-                      CpuBackend be, Border border = Border::Zero);
+                      CpuBackend be, Border border = Border::Zero, int depth = 8);
 
 // A whole image on the host: its two zero-padded ping-pong frames
 // (FrameLayout::make(row_bytes, height, 1); the reference's calloc'd buffers,

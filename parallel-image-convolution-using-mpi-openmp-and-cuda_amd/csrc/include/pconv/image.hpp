@@ -6,7 +6,7 @@
 // 104-124) and indexes it with offset(a,i,j,pitch) (:324-326).  pconv keeps the
 // same idea but sizes it for 16-byte vector access:
 //
-//   * a row holds `row_bytes = width * channels` interleaved bytes;
+//   * a row holds `row_bytes = width * channels * depth / 8` interleaved bytes;
 //   * every frame row is `pitch` bytes: kPadLeft zero bytes, the row, then at
 //     least kPadRight zero bytes (pitch rounded up to kPitchAlign);
 //   * `halo` zero/ghost rows sit above and below the owned rows.
@@ -29,9 +29,11 @@ struct ImageGeom {
   int64_t width = 0;   // pixels per row
   int64_t height = 0;  // rows
   Channels channels = Channels::Grey;
+  int depth = 8;  // bits per sample: 8, or 16 (unsigned, host byte order)
 
   int ch() const { return channel_count(channels); }
-  int64_t row_bytes() const { return width * ch(); }
+  int pixel_bytes() const { return ch() * (depth / 8); }
+  int64_t row_bytes() const { return width * pixel_bytes(); }
   int64_t bytes() const { return row_bytes() * height; }
   int64_t pixels() const { return width * height; }
   void validate() const;

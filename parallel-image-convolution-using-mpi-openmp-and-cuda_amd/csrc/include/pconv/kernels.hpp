@@ -98,6 +98,11 @@ struct StencilLaunch {
   // kernels only (they apply it at every fused step): Auto routes every step
   // count to them, the single-step variants reject it.
   Border border = Border::Zero;
+  // Bits per sample, 8 | 16.  16: rows hold unsigned 16-bit samples in host
+  // byte order, a pixel is 2 x channels bytes, row_bytes and every
+  // ImageDims::row_bytes are whole pixels; the gaussian only, on the 16-bit
+  // temporal kernel (kernels/stencil_swar16.hip) for every step count.
+  int depth = 8;
   ImageSet images;
 };
 
@@ -158,7 +163,8 @@ bool supports_fusion(const Filter& f, KernelVariant v);
 // prefetch_kernel.md); 8 everywhere else (RGB's 3x wider horizontal halo makes
 // deeper fusion slower; 1920x2520 RGB 3.5 us/rep at 8 vs 4.0 at 6, 8192^2 RGB
 // within 2 % either way).  Other filters (float temporal kernel): 4.
-int auto_fuse(const Filter& f, KernelVariant v, int64_t frame_bytes, int channels = 0);
+// Depth 16 (the 16-bit gaussian kernel): 8 (docs/PERFORMANCE.md 3.7).
+int auto_fuse(const Filter& f, KernelVariant v, int64_t frame_bytes, int channels = 0, int depth = 8);
 
 // Row copy by the CUs: `rows` rows of `row_bytes` from src (row pitch sp) to
 // dst (row pitch dp); either side may be pinned host memory (the CUs move the
@@ -212,5 +218,15 @@ void clear_float_tuning();
 // tile kernel k_swar, 1: the buffer-op tile kernel k_swar_pf; live: the workgroups of a mixed-size launch
 // (ImageSet::dims) that have output in their image, 0 for a uniform launch.
 std::vector<std::pair<std::vector<int64_t>, SwarShape>> swar_tuned();
+
+// The 16-bit gaussian kernel's family (kernels/stencil_swar16.hip): lw is the
+// SAMPLES per lane (4 or 8: 8- or 16-byte lane loads), one column strip per
+// lane.  Its shapes (largest tile first), the override (lw = 0: back to the
+// pick / tuner; an unknown shape is an error) and its tuned entries:
+// ({channels, steps, rows, row_bytes, step_form, batch, live}, shape).
+// clear_swar_tuning() forgets them too; swar_tuned() never lists them.
+std::vector<SwarShape> swar16_shapes();
+void set_swar16_shape(int lw, int m, int nw);
+std::vector<std::pair<std::vector<int64_t>, SwarShape>> swar16_tuned();
 
 }  // namespace pconv

@@ -194,6 +194,7 @@ void launch_ch(const Filter& f, const StencilLaunch& a, uint64_t* counter, hipSt
 
 void launch_residual(const Filter& f, Channels ch, const StencilLaunch& a_in, uint64_t* counter, hipStream_t stream) {
   StencilLaunch a = a_in;
+  PCONV_CHECK(a.depth == 8, "launch_residual: depth 16 not supported (no residual kernel for 16-bit samples)");
   check_image_set("launch_residual", a, channel_count(ch));  // on the rows as given
   // rows outside the global image are no part of the map (launch_stencil's clip)
   a.r0 = std::max(a.r0, -a.g_row0);

@@ -224,8 +224,10 @@ bool supports_fusion(const Filter& f, KernelVariant v) {
   return v == KernelVariant::Auto || v == KernelVariant::FloatTemporal;
 }
 
-int auto_fuse(const Filter& f, KernelVariant v, int64_t frame_bytes, int channels) {
+int auto_fuse(const Filter& f, KernelVariant v, int64_t frame_bytes, int channels, int depth) {
   if (!supports_fusion(f, v)) return 1;
+  // the 16-bit gaussian kernel: a policy until its fuse sweep is measured (docs/PERFORMANCE.md 3.7)
+  if (depth == 16) return 8;
   // float temporal kernel (gpurun_out/r03/g/float_sweep.jsonl, tuned shapes):
   // grey 1920x2520 box 3.5 us/rep at 8 vs 3.9 at 4; RGB 8.0 at 4 vs 9.5 at 8
   if (!f.binomial121) return channels == 1 ? 8 : 4;
@@ -252,12 +254,19 @@ bool resolve_launch(const Filter& f, StencilLaunch& a, KernelVariant& v) {
   a.r0 = std::max(a.r0, -a.g_row0);
   a.r1 = std::min(a.r1, a.height - a.g_row0);
   if (a.r1 <= a.r0) return false;
+  // 16-bit samples: the gaussian on its own temporal kernel, whatever the step count
+  if (a.depth == 16 && v == KernelVariant::Auto && f.binomial121) v = KernelVariant::Temporal;
   const bool fused = a.steps > 1 || a.border != Border::Zero || !a.images.single();
   if (v == KernelVariant::Auto)
     v = f.binomial121 ? (fused ? KernelVariant::Temporal : KernelVariant::Binomial)
                       : (fused ? KernelVariant::FloatTemporal
                                : (f.int_exact ? KernelVariant::Int9 : KernelVariant::Float9));
   return true;
+}
+
+// Whether the 16-bit kernel takes the launch (what launch_stencil checks by name).
+bool depth16_launch_ok(const Filter& f, Channels ch, const StencilLaunch& a, KernelVariant v) {
+  return a.depth == 16 && f.binomial121 && v == KernelVariant::Temporal && a.row_bytes % (2 * channel_count(ch)) == 0;
 }
 
 }  // namespace
@@ -268,6 +277,10 @@ void prepare_stencil(const Filter& f, Channels ch, const StencilLaunch& a_in, hi
   StencilLaunch a = a_in;
   if (!resolve_launch(f, a, v) || a.steps > kMaxFusedSteps) return;
   if (a.images.has_table()) return;  // an active-image launch never tunes: nothing to settle
+  if (a.depth != 8) {
+    if (depth16_launch_ok(f, ch, a, v)) prepare_swar16(a, ch, stream);
+    return;
+  }
   if (v == KernelVariant::Temporal && f.binomial121) prepare_swar(a, ch, stream);
   if (v == KernelVariant::FloatTemporal) prepare_float_temporal(f, ch, a, stream);
 }
@@ -280,7 +293,15 @@ void launch_stencil(const Filter& f, Channels ch, const StencilLaunch& a_in, hip
   check_frame_access("launch_stencil", a, a.src && a.dst && a.src != a.dst, a.steps);
   PCONV_CHECK(a.row_bytes < (int64_t(1) << 31) && a.r1 - a.frame_lo < (int64_t(1) << 31),
               "launch_stencil: geometry exceeds 32-bit kernel indices");
-  check_image_set("launch_stencil", a_in, channel_count(ch));  // on the rows as given
+  PCONV_CHECK(a.depth == 8 || a.depth == 16, "launch_stencil: depth must be 8 or 16");
+  if (a.depth == 16) {
+    PCONV_CHECK(f.binomial121, "launch_stencil: depth 16 runs the gaussian filter only, not '" + f.name + "'");
+    PCONV_CHECK(v == KernelVariant::Temporal, "launch_stencil: depth 16 not supported by kernel '" +
+                                                  std::string(kernel_variant_name(v)) + "' (auto and temporal only)");
+    PCONV_CHECK(a.row_bytes % (2 * channel_count(ch)) == 0,
+                "launch_stencil: row_bytes " + std::to_string(a.row_bytes) + " is no whole number of depth-16 pixels");
+  }
+  check_image_set("launch_stencil", a_in, channel_count(ch) * (a.depth / 8));  // on the rows as given
   if (v != KernelVariant::Temporal && v != KernelVariant::FloatTemporal)
     check_temporal_only("launch_stencil", kernel_variant_name(v),
                         {{"active", a.images.has_table()},
@@ -298,7 +319,10 @@ void launch_stencil(const Filter& f, Channels ch, const StencilLaunch& a_in, hip
     PCONV_CHECK(f.binomial121, "temporal kernel requires the gaussian filter");
     PCONV_CHECK(a.steps <= kMaxFusedSteps, "temporal kernel: too many fused steps");
     PCONV_CHECK(a.height < (int64_t(1) << 30) && a.g_row0 < (int64_t(1) << 30), "temporal kernel: rows exceed 2^30");
-    launch_swar(a, ch, stream);
+    if (a.depth == 16)
+      launch_swar16(a, ch, stream);
+    else
+      launch_swar(a, ch, stream);
     PCONV_HIP_CHECK(hipGetLastError());
     return;
   }

@@ -596,6 +596,7 @@ void launch_ft(const StencilLaunch& a, const FloatTaps& tp, hipStream_t s, bool 
 }
 
 void float_temporal(const Filter& f, Channels ch, const StencilLaunch& a, hipStream_t stream, bool launch) {
+  PCONV_CHECK(a.depth == 8, "launch_float_temporal: depth 16 not supported (the gaussian on the temporal kernel only)");
   PCONV_CHECK(a.steps >= 1 && a.steps <= kMaxFusedSteps, "float temporal kernel: steps out of range");
   PCONV_CHECK(a.height < (int64_t(1) << 30) && a.g_row0 < (int64_t(1) << 30), "float temporal kernel: rows exceed 2^30");
   PCONV_CHECK(a.row_bytes > 0 && a.row_bytes < (int64_t(1) << 30), "float temporal kernel: row bytes out of range");

@@ -63,35 +63,6 @@
 namespace pconv {
 namespace {
 
-// The `steps` repetitions of a tile in one of two step forms (the tuner
-// times both per launch geometry):
-//   0: one swar_step per repetition, truncating every step;
-//   1: steps in pairs keeping 16 x the truncated value in between (one AND
-//      instead of shift + AND every other step), one barrier per step.
-// Form 1 costs registers (up to +40 VGPRs on grey tiles).  A third form with
-// ONE barrier per pair of steps (two boundary rows per side exchanged, one
-// ghost row per side recomputed) never won a tuning and forced it measured
-// 0-8 % slower than form 1 (round 5: headline 3.645 vs 3.377 us/rep,
-// 32768^2 grey 113.8 vs 109.2; profiles/r05/d/form_ab.jsonl): removed.
-template <int CH, int NP, int M, int NW, int FORM, bool REP>
-__device__ __forceinline__ void run_steps(u32 (&D)[M][NP], uint4 (&lds)[2][NW][2][NP / 4][64], int steps, int w,
-                                          int lane, bool needs_mask, const u32 (&cm)[NP], int out_top, int out_bot,
-                                          const EdgeFix<CH, NP, REP>& ef) {
-  if constexpr (REP)
-    if (out_top > 0 || out_bot < M) edge_rows<NP, M>(D, out_top, out_bot);  // the loaded rows' out-of-image neighbours
-  if constexpr (FORM == 1) {
-    int s = 0;
-    for (; s + 2 <= steps; s += 2) {
-      swar_step<CH, NP, M, NW, 1, REP>(D, lds, 0, w, lane, needs_mask, cm, out_top, out_bot, ef);
-      swar_step<CH, NP, M, NW, 2, REP>(D, lds, 1, w, lane, needs_mask, cm, out_top, out_bot, ef);
-    }
-    if (s < steps) swar_step<CH, NP, M, NW, 0, REP>(D, lds, 0, w, lane, needs_mask, cm, out_top, out_bot, ef);
-  } else {
-    for (int s = 0; s < steps; ++s)
-      swar_step<CH, NP, M, NW, 0, REP>(D, lds, s & 1, w, lane, needs_mask, cm, out_top, out_bot, ef);
-  }
-}
-
 // The replicate border's per-lane state (swar_device.hpp, EdgeFix) for a tile
 // whose strips start at byte columns baseA / baseB and whose wave's register
 // row 0 is frame row row_base.  `h` is set only in tiles that hold the image's
@@ -605,6 +576,8 @@ KernelRes kernel_res(const SwarShape& sh, int ch, int form) {
 }  // namespace
 
 void set_xcd_swizzle(bool on) { g_xcd_swizzle.store(on ? 1 : 0, std::memory_order_relaxed); }
+bool swar_xcd_swizzle() { return xcd_swizzle_enabled(); }
+int swar_alt_mode() { return alt_mode(); }
 void set_swar_alt(int mode) { g_alt_mode.store(mode < 0 ? -1 : std::min(mode, 1), std::memory_order_relaxed); }
 void set_prefetch_mode(int mode) { g_pf_mode.store(mode < 0 ? -1 : mode > 0 ? 1 : 0, std::memory_order_relaxed); }
 
@@ -825,6 +798,7 @@ void clear_swar_tuning() {
     g_tuned.clear();
   }
   clear_float_tuning();
+  clear_swar16_tuning();
 }
 
 std::vector<std::pair<std::vector<int64_t>, SwarShape>> swar_tuned() {

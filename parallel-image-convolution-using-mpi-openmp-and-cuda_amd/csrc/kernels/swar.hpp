@@ -38,5 +38,16 @@ void set_swar_alt(int mode);
 // (default), 0 never, 1 forced; with the mode forced, a shape set by
 // set_swar_shape that it instantiates is used as is (tests).
 void set_prefetch_mode(int mode);
+// The two settings as the 16-bit kernel's launches read them (stencil_swar16.hip).
+bool swar_xcd_swizzle();
+int swar_alt_mode();
+
+// The 16-bit gaussian (kernels/stencil_swar16.hip): a.depth == 16, every step
+// count up to kMaxFusedSteps.  Shape: forced (set_swar16_shape), else tuned on
+// first use over the shapes that run the launch x both step forms, else the
+// first shape whose grid fills the chip.
+void launch_swar16(const StencilLaunch& a, Channels ch, hipStream_t stream);
+void prepare_swar16(const StencilLaunch& a, Channels ch, hipStream_t stream);
+void clear_swar16_tuning();
 
 }  // namespace pconv

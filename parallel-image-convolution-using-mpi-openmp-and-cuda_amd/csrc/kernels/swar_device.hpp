@@ -1,7 +1,10 @@
 // Device helpers of the SWAR-32 gaussian tile kernels (stencil_swar.hip):
-// the byte-pair layout, the horizontal [1,2,1] with DPP lane crossing, and one
-// interior-first repetition of a wave's register rows.  See stencil_swar.hip
-// for the layout and the measurements behind these forms.
+// the byte-pair layout, the horizontal [1,2,1] with DPP lane crossing, one
+// interior-first repetition of a wave's register rows and the loop over a
+// launch's repetitions.  See stencil_swar.hip for the layout and the
+// measurements behind these forms.  The 16-bit kernel (stencil_swar16.hip)
+// runs the same step on one sample per register (field width 1 of trunc_sum)
+// with its own load / unpack / store shell.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -223,16 +226,25 @@ __device__ __forceinline__ void edge_rows(u32 (&D)[M][NP], int out_top, int out_
 // then sums values < 2^12 into fields < 2^16); 2 floor(S/256) of such a step.
 // Out-of-image rows and columns are re-zeroed after every step (under the
 // replicate border too: its corrections rely on those zeros, see EdgeFix).
-template <int MODE>
+// FW: fields per register.  2: the byte pairs above.  1: one 16-bit sample in
+// the whole u32 (stencil_swar16.hip) — nothing to mask: a step sum stays below
+// 16 x 65535 < 2^20, a sum of x16 intermediates below 2^28.
+template <int MODE, int FW = 2>
 __device__ __forceinline__ u32 trunc_sum(u32 S) {
-  if constexpr (MODE == 0) return (S >> 4) & 0x00ff00ffu;
-  else if constexpr (MODE == 1) return S & 0x0ff00ff0u;
-  else return (S >> 8) & 0x00ff00ffu;
+  if constexpr (FW == 1) {
+    if constexpr (MODE == 0) return S >> 4;
+    else if constexpr (MODE == 1) return S & ~0xfu;
+    else return S >> 8;
+  } else {
+    if constexpr (MODE == 0) return (S >> 4) & 0x00ff00ffu;
+    else if constexpr (MODE == 1) return S & 0x0ff00ff0u;
+    else return (S >> 8) & 0x00ff00ffu;
+  }
 }
 
 // lds[parity][wave][2][quad][lane]: slot 0 = the wave's top row, slot 1 its
 // bottom row.
-template <int CH, int NP, int M, int NW, int MODE = 0, bool REP = false>
+template <int CH, int NP, int M, int NW, int MODE = 0, bool REP = false, int FW = 2>
 __device__ __forceinline__ void swar_step(u32 (&D)[M][NP], uint4 (&lds)[2][NW][2][NP / 4][64], int par, int w,
                                              int lane, bool needs_mask, const u32 (&cm)[NP], int out_top,
                                              int out_bot, const EdgeFix<CH, NP, REP>& ef) {
@@ -262,7 +274,7 @@ __device__ __forceinline__ void swar_step(u32 (&D)[M][NP], uint4 (&lds)[2][NW][2
 #pragma unroll
     for (int k = 0; k < NP; ++k) {
       const u32 Sn = keep(Hc[k] + Hn[k]);
-      D[i][k] = trunc_sum<MODE>(Sc[k] + Sn);
+      D[i][k] = trunc_sum<MODE, FW>(Sc[k] + Sn);
       Sc[k] = Sn;
       Hc[k] = Hn[k];
     }
@@ -297,8 +309,8 @@ __device__ __forceinline__ void swar_step(u32 (&D)[M][NP], uint4 (&lds)[2][NW][2
     horiz_b<CH, NP, REP>(B, Hb, ef);
 #pragma unroll
     for (int k = 0; k < NP; ++k) {
-      D[0][k] = trunc_sum<MODE>(keep(Ha[k] + H0[k]) + S01[k]);
-      D[M - 1][k] = trunc_sum<MODE>(Sc[k] + keep(Hc[k] + Hb[k]));
+      D[0][k] = trunc_sum<MODE, FW>(keep(Ha[k] + H0[k]) + S01[k]);
+      D[M - 1][k] = trunc_sum<MODE, FW>(Sc[k] + keep(Hc[k] + Hb[k]));
     }
   }
   if (needs_mask) {
@@ -314,6 +326,35 @@ __device__ __forceinline__ void swar_step(u32 (&D)[M][NP], uint4 (&lds)[2][NW][2
 #pragma unroll
         for (int k = 0; k < NP; ++k) D[i][k] = 0;
     if constexpr (REP) edge_rows<NP, M>(D, out_top, out_bot);
+  }
+}
+
+// The `steps` repetitions of a tile in one of two step forms (the tuner
+// times both per launch geometry):
+//   0: one swar_step per repetition, truncating every step;
+//   1: steps in pairs keeping 16 x the truncated value in between (one AND
+//      instead of shift + AND every other step), one barrier per step.
+// Form 1 costs registers (up to +40 VGPRs on grey tiles).  A third form with
+// ONE barrier per pair of steps (two boundary rows per side exchanged, one
+// ghost row per side recomputed) never won a tuning and forced it measured
+// 0-8 % slower than form 1 (round 5: headline 3.645 vs 3.377 us/rep,
+// 32768^2 grey 113.8 vs 109.2; profiles/r05/d/form_ab.jsonl): removed.
+template <int CH, int NP, int M, int NW, int FORM, bool REP, int FW = 2>
+__device__ __forceinline__ void run_steps(u32 (&D)[M][NP], uint4 (&lds)[2][NW][2][NP / 4][64], int steps, int w,
+                                          int lane, bool needs_mask, const u32 (&cm)[NP], int out_top, int out_bot,
+                                          const EdgeFix<CH, NP, REP>& ef) {
+  if constexpr (REP)
+    if (out_top > 0 || out_bot < M) edge_rows<NP, M>(D, out_top, out_bot);  // the loaded rows' out-of-image neighbours
+  if constexpr (FORM == 1) {
+    int s = 0;
+    for (; s + 2 <= steps; s += 2) {
+      swar_step<CH, NP, M, NW, 1, REP, FW>(D, lds, 0, w, lane, needs_mask, cm, out_top, out_bot, ef);
+      swar_step<CH, NP, M, NW, 2, REP, FW>(D, lds, 1, w, lane, needs_mask, cm, out_top, out_bot, ef);
+    }
+    if (s < steps) swar_step<CH, NP, M, NW, 0, REP, FW>(D, lds, 0, w, lane, needs_mask, cm, out_top, out_bot, ef);
+  } else {
+    for (int s = 0; s < steps; ++s)
+      swar_step<CH, NP, M, NW, 0, REP, FW>(D, lds, s & 1, w, lane, needs_mask, cm, out_top, out_bot, ef);
   }
 }
 

@@ -43,6 +43,7 @@ ImageGeom geom_of(const CliConfig& c) {
   g.width = c.width;
   g.height = c.height;
   g.channels = c.channels;
+  g.depth = c.depth;
   g.validate();
   return g;
 }
@@ -65,7 +66,7 @@ EngineOptions engine_options(const CliConfig& c, const ImageGeom& g, int world, 
   o.overlap = c.overlap;
   o.use_graph = c.graph && world == 1;
   const bool fusable = supports_fusion(f, c.variant);
-  o.fuse = c.fuse > 0 ? c.fuse : auto_fuse(f, c.variant, g.row_bytes() * (g.height / std::max(1, world)), g.ch());
+  o.fuse = c.fuse > 0 ? c.fuse : auto_fuse(f, c.variant, g.row_bytes() * (g.height / std::max(1, world)), g.ch(), g.depth);
   if (!fusable) o.fuse = 1;
   o.fuse = std::max(1, std::min(o.fuse, std::max(1, c.reps)));
   if (c.halo > 0) {
@@ -191,7 +192,7 @@ struct JobCache {
 
   BandEngine& engine(const ImageGeom& g, const Filter& f, const EngineOptions& o, const std::string& fname,
                      bool* fresh) {
-    const Key k{g.width, g.height, channel_count(g.channels), fname, o.fuse, o.halo_depth,
+    const Key k{g.width, g.height, g.pixel_bytes(), fname, o.fuse, o.halo_depth,
                 static_cast<int>(o.variant), o.overlap, o.use_graph, o.kernel_copies,
                 static_cast<int>(o.border)};  // an engine applies ONE border rule to every launch
     for (auto it = engines.begin(); it != engines.end(); ++it)
@@ -1265,7 +1266,7 @@ std::string report_json(const CliConfig& c, const AppReport& r) {
   const double px =
       static_cast<double>(c.width) * static_cast<double>(c.height) * c.frames * (r.reps_done >= 0 ? r.reps_done : c.reps);
   os << "{\"width\": " << c.width << ", \"height\": " << c.height << ", \"channels\": \""
-     << channels_name(c.channels) << "\", \"frames\": " << c.frames << ", \"reps\": " << c.reps << ", \"filter\": \"" << c.filter
+     << channels_name(c.channels) << "\", \"depth\": " << c.depth << ", \"frames\": " << c.frames << ", \"reps\": " << c.reps << ", \"filter\": \"" << c.filter
      << "\", \"border\": \"" << border_name(c.border) << "\", \"backend\": \""
      << (c.backend == Backend::Hip ? "hip" : c.backend == Backend::Omp ? "omp" : c.backend == Backend::Auto ? "auto" : "cpu")
      << "\", \"gpus\": " << r.gpus << ", \"kernel\": \"" << r.kernel << "\", \"halo\": " << r.halo

@@ -19,6 +19,10 @@ BatchEngine::BatchEngine(const ImageGeom& geom, const Filter& filter, int capaci
   const KernelVariant v = opt.variant;
   PCONV_CHECK(v == KernelVariant::Auto || v == KernelVariant::Temporal || v == KernelVariant::FloatTemporal,
               "BatchEngine: batch not supported by kernel '" + std::string(kernel_variant_name(v)) + "'");
+  if (geom_.depth == 16) {
+    PCONV_CHECK(filter_.binomial121, "BatchEngine: depth 16 runs the gaussian filter only, not '" + filter_.name + "'");
+    PCONV_CHECK(v != KernelVariant::FloatTemporal, "BatchEngine: depth 16 not supported by kernel 'float_temporal'");
+  }
   PlanConfig c;
   c.fuse = opt.fuse;
   c = normalize_plan_config(c, 0, kMaxFusedSteps);
@@ -174,6 +178,7 @@ StencilLaunch BatchEngine::base_launch(int n) const {
   a.g_row0 = 0;
   a.height = geom_.height;
   a.border = opt_.border;
+  a.depth = geom_.depth;
   a.images.frames = n;
   a.images.stride = stride_;
   if (!sizes_.empty()) {

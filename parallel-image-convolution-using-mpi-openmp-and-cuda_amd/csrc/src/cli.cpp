@@ -47,6 +47,11 @@ std::string help_text(const std::string& prog) {
          "  --kernel {auto,binomial,temporal,int9,float9,float_temporal}\n"
          "  --out PATH                output file (default: blur_<image> next to the input)\n"
          "  --synthetic SEED          use a deterministic random image instead of reading the file\n"
+         "  --depth {8,16}            bits per sample (default 8).  16: the file holds unsigned little-endian\n"
+         "                            16-bit samples (width x height x channels x 2 bytes per frame); gaussian\n"
+         "                            only, --backend hip (1 GPU) | cpu | omp.  Not with another --filter,\n"
+         "                            --gpus > 1, --server, --bench, --backend auto, --converge-every,\n"
+         "                            --checkpoint-every, --graph, --kernel other than auto | temporal\n"
          "  --frames N                the file holds N images of width x height back to back (default 1); each\n"
          "                            is convolved on its own and the output has the same layout.  hip: all\n"
          "                            frames advance in the same fused launches on 1 GPU; --synthetic makes\n"
@@ -152,6 +157,10 @@ CliConfig parse_cli(const std::vector<std::string>& args) {
     } else if (a == "--synthetic") {
       c.synthetic = true;
       c.seed = static_cast<uint64_t>(parse_int(next("--synthetic"), "--synthetic", 0, INT64_MAX));
+    } else if (a == "--depth") {
+      const std::string v = next("--depth");
+      if (v != "8" && v != "16") PCONV_FAIL("invalid --depth '" + v + "' (8|16)");
+      c.depth = v == "16" ? 16 : 8;
     } else if (a == "--frames") {
       c.frames = static_cast<int>(parse_int(next("--frames"), "--frames", 1, 1 << 20));
     } else if (a == "--check") {
@@ -251,6 +260,19 @@ CliConfig parse_cli(const std::vector<std::string>& args) {
     if (c.checkpoint_every > 0) refuse("--checkpoint-every");
     if (c.converge_every > 0) refuse("--converge-every");
     if (c.graph) refuse("--graph (a batch is not captured into a hipGraph)");
+  }
+  if (c.depth == 16) {
+    const auto refuse = [](const std::string& what) { PCONV_FAIL("--depth 16 cannot be combined with " + what); };
+    if (c.filter != "gaussian") refuse("--filter " + c.filter + " (depth 16 runs the gaussian only)");
+    if (c.gpus > 1) refuse("--gpus above 1");
+    if (!c.server.empty()) refuse("--server");
+    if (c.bench_steps > 0) refuse("--bench");
+    if (c.backend == Backend::Auto) refuse("--backend auto");
+    if (c.converge_every > 0) refuse("--converge-every");
+    if (c.checkpoint_every > 0) refuse("--checkpoint-every");
+    if (c.graph) refuse("--graph");
+    if (c.variant != KernelVariant::Auto && c.variant != KernelVariant::Temporal)
+      refuse("--kernel other than auto|temporal");
   }
   if (c.emulate_world > 0 && (c.bench_steps == 0 || c.gpus != 1))
     PCONV_FAIL("--emulate needs --bench and --gpus 1 (one process times one rank of the split)");

@@ -124,6 +124,7 @@ int Filter::abs_sum() const {
 void ImageGeom::validate() const {
   PCONV_CHECK(width > 0 && height > 0, "image width and height must be positive");
   PCONV_CHECK(width <= (int64_t(1) << 30) && height <= (int64_t(1) << 30), "image dimension too large");
+  PCONV_CHECK(depth == 8 || depth == 16, "image depth must be 8 or 16 bits per sample");
 }
 
 FrameLayout FrameLayout::make(int64_t row_bytes, int64_t rows, int64_t halo) {
@@ -189,14 +190,14 @@ std::vector<ImageDims> image_dims_table(const ImageGeom& env, int capacity, cons
                 "BatchEngine::upload_sized: image " + std::to_string(b) + " (" + std::to_string(z.width) + "x" +
                     std::to_string(z.height) + ") does not lie within the envelope " + std::to_string(env.width) +
                     "x" + std::to_string(env.height));
-    out.push_back(ImageDims{static_cast<int32_t>(z.width * env.ch()), static_cast<int32_t>(z.height)});
+    out.push_back(ImageDims{static_cast<int32_t>(z.width * env.pixel_bytes()),static_cast<int32_t>(z.height)});
   }
   return out;
 }
 
 int64_t packed_bytes(const ImageGeom& env, const std::vector<ImageSize>& sizes) {
   int64_t total = 0;
-  for (const auto& z : sizes) total += z.width * env.ch() * z.height;
+  for (const auto& z : sizes) total += z.width * env.pixel_bytes() * z.height;
   return total;
 }
 

@@ -61,6 +61,18 @@ void row_binomial(const uint8_t* a, const uint8_t* b, const uint8_t* c, uint8_t*
     row_binomial_base<CH>(a, b, c, o, n, scratch.data());
 }
 
+// The same two passes on 16-bit samples (depth 16): a vertical sum is at most
+// 4 x 65535, the full sum 16 x 65535 < 2^20, so the scratch row is 32 bits
+// wide.  Baseline build only.
+template <int CH>
+void row_binomial(const uint16_t* a, const uint16_t* b, const uint16_t* c, uint16_t* o, int64_t n) {
+  thread_local std::vector<uint32_t> scratch;
+  if (scratch.size() < static_cast<size_t>(n + 2 * CH)) scratch.resize(static_cast<size_t>(n + 2 * CH));
+  uint32_t* v = scratch.data();
+  for (int64_t x = -CH; x < n + CH; ++x) v[x + CH] = uint32_t{a[x]} + 2 * uint32_t{b[x]} + uint32_t{c[x]};
+  for (int64_t x = 0; x < n; ++x) o[x] = static_cast<uint16_t>((v[x] + 2 * v[x + CH] + v[x + 2 * CH]) >> 4);
+}
+
 // Integer-exact custom filters (non-negative taps, power-of-two divisor).
 #define PCONV_ROW_INT_BODY                                                                          \
   const int t0 = t[0], t1 = t[1], t2 = t[2], t3 = t[3], t4 = t[4], t5 = t[5], t6 = t[6], t7 = t[7], \
@@ -137,9 +149,9 @@ void row_float(const Filter& f, const uint8_t* a, const uint8_t* b, const uint8_
 // Replicate border: row `p` (n bytes) with its first and last pixel repeated
 // once on either side, in `buf` (n + 2 CH bytes); returns the column-0 pointer.
 // The source frame is only read: its pad columns and ghost rows stay as they are.
-template <int CH>
-const uint8_t* edge_padded(const uint8_t* p, int64_t n, uint8_t* buf) {
-  std::memcpy(buf + CH, p, static_cast<size_t>(n));
+template <int CH, class T>
+const T* edge_padded(const T* p, int64_t n, T* buf) {
+  std::memcpy(buf + CH, p, static_cast<size_t>(n) * sizeof(T));
   for (int k = 0; k < CH; ++k) {
     buf[k] = p[k];
     buf[CH + n + k] = p[n - CH + k];
@@ -148,6 +160,11 @@ const uint8_t* edge_padded(const uint8_t* p, int64_t n, uint8_t* buf) {
 }
 
 // One output row from its three input rows (column -CH .. n + CH readable).
+// 16-bit samples: the gaussian only (cpu_step refuses the others by name).
+template <int CH>
+void eval_row(const Filter&, const uint16_t* a, const uint16_t* b, const uint16_t* c, uint16_t* o, int64_t n) {
+  row_binomial<CH>(a, b, c, o, n);
+}
 template <int CH>
 void eval_row(const Filter& f, const uint8_t* a, const uint8_t* b, const uint8_t* c, uint8_t* o, int64_t n) {
   if (f.binomial121)
@@ -162,17 +179,24 @@ void eval_row(const Filter& f, const uint8_t* a, const uint8_t* b, const uint8_t
 // to the GLOBAL image — the row above global row 0 is row 0, the row below
 // the last is the last; columns through padded copies, so the same row
 // kernels (integer / float, baseline / AVX2) serve.
-template <int CH>
+// Frame row r as samples of type T (uint8_t, or uint16_t at depth 16: a frame's
+// data column 0 and pitch are 16-byte multiples, so the rows are aligned).
+template <class T>
+const T* row_ptr(const FrameLayout& lay, const uint8_t* frame, int64_t r) {
+  return reinterpret_cast<const T*>(frame + lay.offset(r));
+}
+
+template <int CH, class T>
 void replicate_rows(const FrameLayout& lay, const uint8_t* src, int64_t r, int64_t g_row0, int64_t height,
-                    const uint8_t*& a, const uint8_t*& b, const uint8_t*& c) {
-  const int64_t n = lay.row_bytes;
-  thread_local std::vector<uint8_t> rows3;
+                    const T*& a, const T*& b, const T*& c) {
+  const int64_t n = lay.row_bytes / static_cast<int64_t>(sizeof(T));
+  thread_local std::vector<T> rows3;
   const size_t w = static_cast<size_t>(n + 2 * CH);
   if (rows3.size() < 3 * w) rows3.resize(3 * w);
   const int64_t g = g_row0 + r;
-  const uint8_t* pb = src + lay.offset(r);
-  const uint8_t* pa = g - 1 >= 0 ? src + lay.offset(r - 1) : pb;
-  const uint8_t* pc = g + 1 < height ? src + lay.offset(r + 1) : pb;
+  const T* pb = row_ptr<T>(lay, src, r);
+  const T* pa = g - 1 >= 0 ? row_ptr<T>(lay, src, r - 1) : pb;
+  const T* pc = g + 1 < height ? row_ptr<T>(lay, src, r + 1) : pb;
   a = edge_padded<CH>(pa, n, rows3.data());
   c = edge_padded<CH>(pc, n, rows3.data() + 2 * w);
   b = edge_padded<CH>(pb, n, rows3.data() + w);
@@ -182,19 +206,19 @@ void replicate_rows(const FrameLayout& lay, const uint8_t* src, int64_t r, int64
 // Replicate: replicate_rows.  Zero: the frame's rows as they are (its ghost
 // rows and pad columns are the border), unless zero_outside: then a row
 // outside the global image is a row of zeros, whatever the frame holds there.
-template <int CH>
+template <int CH, class T>
 void input_rows(const FrameLayout& lay, const uint8_t* src, int64_t r, Border border, int64_t g_row0, int64_t height,
-                bool zero_outside, const uint8_t*& a, const uint8_t*& b, const uint8_t*& c) {
-  a = src + lay.offset(r - 1);
-  b = src + lay.offset(r);
-  c = src + lay.offset(r + 1);
+                bool zero_outside, const T*& a, const T*& b, const T*& c) {
+  a = row_ptr<T>(lay, src, r - 1);
+  b = row_ptr<T>(lay, src, r);
+  c = row_ptr<T>(lay, src, r + 1);
   if (border == Border::Replicate) {
     replicate_rows<CH>(lay, src, r, g_row0, height, a, b, c);
   } else if (zero_outside) {
     const int64_t g = g_row0 + r;
     if (g - 1 < 0 || g + 1 >= height) {
-      thread_local std::vector<uint8_t> zeros;
-      const size_t w = static_cast<size_t>(lay.row_bytes + 2 * CH);
+      thread_local std::vector<T> zeros;
+      const size_t w = static_cast<size_t>(lay.row_bytes / sizeof(T) + 2 * CH);
       if (zeros.size() < w) zeros.assign(w, 0);
       if (g - 1 < 0) a = zeros.data() + CH;
       if (g + 1 >= height) c = zeros.data() + CH;
@@ -219,13 +243,13 @@ uint64_t sum_rows(int64_t r0, int64_t r1, int64_t n, CpuBackend be, Body&& body)
   return total;
 }
 
-template <int CH>
+template <int CH, class T = uint8_t>
 void step_rows(const Filter& f, const FrameLayout& lay, const uint8_t* src, uint8_t* dst, int64_t r0, int64_t r1,
                CpuBackend be, Border border, int64_t g_row0, int64_t height) {
   (void)sum_rows(r0, r1, lay.row_bytes, be, [&](int64_t r) -> uint64_t {
-    const uint8_t *a, *b, *c;
+    const T *a, *b, *c;
     input_rows<CH>(lay, src, r, border, g_row0, height, false, a, b, c);
-    eval_row<CH>(f, a, b, c, dst + lay.offset(r), lay.row_bytes);
+    eval_row<CH>(f, a, b, c, reinterpret_cast<T*>(dst + lay.offset(r)), lay.row_bytes / static_cast<int64_t>(sizeof(T)));
     return 0;
   });
 }
@@ -272,27 +296,35 @@ uint64_t cpu_residual(const Filter& f, Channels ch, const FrameLayout& lay, cons
 }
 
 void cpu_step(const Filter& f, Channels ch, const FrameLayout& lay, const uint8_t* src_frame, uint8_t* dst_frame,
-              int64_t r0, int64_t r1, CpuBackend be, Border border, int64_t g_row0, int64_t height) {
+              int64_t r0, int64_t r1, CpuBackend be, Border border, int64_t g_row0, int64_t height, int depth) {
+  PCONV_CHECK(depth == 8 || depth == 16, "cpu_step: depth must be 8 or 16");
+  if (depth == 16) {
+    PCONV_CHECK(f.binomial121, "cpu_step: depth 16 runs the gaussian filter only, not '" + f.name + "'");
+    PCONV_CHECK(lay.row_bytes % (2 * channel_count(ch)) == 0, "cpu_step: row bytes are no whole depth-16 pixels");
+  }
   PCONV_CHECK(r0 >= -lay.halo + 1 && r1 <= lay.rows + lay.halo - 1 && r0 <= r1, "cpu_step: rows out of frame");
   if (height < 0) height = g_row0 + lay.rows;  // the frame's owned rows end the image
   if (border != Border::Zero)
     PCONV_CHECK(r0 >= r1 || (g_row0 + r0 >= 0 && g_row0 + r1 <= height),
                 "cpu_step: a non-zero border computes rows of the global image only");
   with_channels(ch, [&](auto chn) {
-    step_rows<decltype(chn)::value>(f, lay, src_frame, dst_frame, r0, r1, be, border, g_row0, height);
+    if (depth == 16)
+      step_rows<decltype(chn)::value, uint16_t>(f, lay, src_frame, dst_frame, r0, r1, be, border, g_row0, height);
+    else
+      step_rows<decltype(chn)::value>(f, lay, src_frame, dst_frame, r0, r1, be, border, g_row0, height);
   });
 }
 
 void cpu_fused_launch(const Filter& f, Channels ch, const FrameLayout& lay, const uint8_t* src_frame,
                       uint8_t* dst_frame, int64_t lo, int64_t hi, int steps, int64_t g_row0, int64_t height,
-                      CpuBackend be, Border border) {
+                      CpuBackend be, Border border, int depth) {
   PCONV_CHECK(steps >= 1 && lo <= hi, "cpu_fused_launch: bad arguments");
   PCONV_CHECK(lo - steps >= -lay.halo && hi + steps <= lay.rows + lay.halo, "cpu_fused_launch: rows exceed frame");
   if (lo == hi) return;
   if (steps == 1) {
     // Single step never writes rows outside the image: clip like the kernels' caller.
     const int64_t a = std::max(lo, -g_row0), b = std::min(hi, height - g_row0);
-    if (a < b) cpu_step(f, ch, lay, src_frame, dst_frame, a, b, be, border, g_row0, height);
+    if (a < b) cpu_step(f, ch, lay, src_frame, dst_frame, a, b, be, border, g_row0, height, depth);
     return;
   }
   const size_t n = static_cast<size_t>(lay.bytes());
@@ -302,7 +334,7 @@ void cpu_fused_launch(const Filter& f, Channels ch, const FrameLayout& lay, cons
   for (int j = 1; j <= steps; ++j) {
     const int64_t ext = steps - j;
     const int64_t a = std::max(lo - ext, -g_row0), b = std::min(hi + ext, height - g_row0);
-    if (a < b) cpu_step(f, ch, lay, cur, nxt, a, b, be, border, g_row0, height);
+    if (a < b) cpu_step(f, ch, lay, cur, nxt, a, b, be, border, g_row0, height, depth);
     std::swap(cur, nxt);
   }
   for (int64_t r = lo; r < hi; ++r) {
@@ -404,11 +436,13 @@ void HostFrames::release() {
 }
 
 void HostFrames::step() {
-  cpu_step(f_, geom_.channels, lay_, cur_.data(), nxt_.data(), 0, geom_.height, be_, border_, 0, geom_.height);
+  cpu_step(f_, geom_.channels, lay_, cur_.data(), nxt_.data(), 0, geom_.height, be_, border_, 0, geom_.height,
+           geom_.depth);
   cur_.swap(nxt_);  // newest result is always in `cur_` (fixes SURVEY §A3)
 }
 
 uint64_t HostFrames::residual() const {
+  PCONV_CHECK(geom_.depth == 8, "residual: depth 16 not supported (no fixed-point check for 16-bit samples)");
   return cpu_residual(f_, geom_.channels, lay_, cur_.data(), 0, geom_.height, be_, border_, 0, geom_.height);
 }
 

@@ -34,6 +34,13 @@ BandEngine::BandEngine(const ImageGeom& geom, const Band& band, const Filter& fi
                   opt.variant == KernelVariant::Temporal || opt.variant == KernelVariant::FloatTemporal,
               "border '" + std::string(border_name(opt.border)) + "' not supported by kernel '" +
                   std::string(kernel_variant_name(opt.variant)) + "' (temporal and float_temporal only)");
+  if (geom_.depth == 16) {
+    PCONV_CHECK(filter_.binomial121, "depth 16 runs the gaussian filter only, not '" + filter_.name + "'");
+    PCONV_CHECK(opt.variant == KernelVariant::Auto || opt.variant == KernelVariant::Temporal,
+                "depth 16 not supported by kernel '" + std::string(kernel_variant_name(opt.variant)) +
+                    "' (auto and temporal only)");
+    PCONV_CHECK(!opt.use_graph, "depth 16 not supported with graph replay");
+  }
   const PlanConfig c = engine_plan_config(geom_, band_, filter_, opt_);
   opt_.fuse = c.fuse;
   opt_.halo_depth = c.halo_depth;
@@ -190,6 +197,7 @@ StencilLaunch BandEngine::make_launch(const LaunchSpec& l, int cur) const {
   a.g_row0 = band_.y0;
   a.height = geom_.height;
   a.border = opt_.border;
+  a.depth = geom_.depth;
   return a;
 }
 
@@ -697,6 +705,7 @@ Stream own_queue_stream(int device) {
 BandPipeline::BandPipeline(const ImageGeom& geom, const Band& band, const Filter& filter, const EngineOptions& opt,
                            int slots, int concurrent, bool graphs, bool step_graphs, bool slot_comm) {
   PCONV_CHECK(slots >= 1 && slots <= 8, "pipeline slots must be in [1, 8]");
+  PCONV_CHECK(geom.depth == 8, "BandPipeline: depth 16 not supported");
   set_device(opt.device);
   if (graphs) {
     // One stream per slot carries that slot's whole image (H2D, reps, D2H) as
@@ -1092,6 +1101,7 @@ void LocalTransport::exchange(BandEngine& e, int64_t depth, hipStream_t stream) 
 
 LocalCluster::LocalCluster(const ImageGeom& geom, int bands, const Filter& filter, const EngineOptions& opt)
     : geom_(geom) {
+  PCONV_CHECK(geom.depth == 8, "LocalCluster: depth 16 not supported");
   const auto bs = row_bands(geom.height, bands);
   std::vector<BandEngine*> peers;
   for (const auto& b : bs) {

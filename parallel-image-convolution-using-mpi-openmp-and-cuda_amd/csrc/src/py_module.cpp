@@ -45,11 +45,12 @@ HostView host_view(py::buffer b, bool writable) {
   return {static_cast<uint8_t*>(info.ptr), static_cast<int64_t>(info.size)};
 }
 
-ImageGeom make_geom(int64_t w, int64_t h, const std::string& ch) {
+ImageGeom make_geom(int64_t w, int64_t h, const std::string& ch, int depth = 8) {
   ImageGeom g;
   g.width = w;
   g.height = h;
   g.channels = parse_channels(ch);
+  g.depth = depth;
   g.validate();
   return g;
 }
@@ -190,8 +191,8 @@ PYBIND11_MODULE(_pconv_native, m) {
   m.def(
       "cpu_convolve",
       [](py::buffer in, py::buffer out, int64_t w, int64_t h, const std::string& ch, int reps, py::object filter,
-         bool omp, int threads, const std::string& border) {
-        const ImageGeom g = make_geom(w, h, ch);
+         bool omp, int threads, const std::string& border, int depth) {
+        const ImageGeom g = make_geom(w, h, ch, depth);
         const Border bd = parse_border(border);
         const HostView a = host_view(in, false), b = host_view(out, true);
         PCONV_CHECK(a.size == g.bytes() && b.size == g.bytes(), "buffer size does not match the image geometry");
@@ -200,7 +201,8 @@ PYBIND11_MODULE(_pconv_native, m) {
         cpu_convolve(f, g, a.ptr, b.ptr, reps, omp ? CpuBackend::OpenMP : CpuBackend::Serial, threads, bd);
       },
       py::arg("src"), py::arg("dst"), py::arg("width"), py::arg("height"), py::arg("channels"), py::arg("reps"),
-      py::arg("filter") = "gaussian", py::arg("omp") = false, py::arg("threads") = 0, py::arg("border") = "zero");
+      py::arg("filter") = "gaussian", py::arg("omp") = false, py::arg("threads") = 0, py::arg("border") = "zero",
+      py::arg("depth") = 8);
   m.def("default_cpu_threads", &default_cpu_threads,
         "OpenMP team size used when none is set: affinity CPUs capped by the cgroup quota, minus one");
   m.def(
@@ -217,7 +219,7 @@ PYBIND11_MODULE(_pconv_native, m) {
       "cpu_fused_launch",
       [](py::object filter, const std::string& ch, int64_t row_bytes, int64_t rows, int64_t halo, py::buffer src,
          py::buffer dst, int64_t lo, int64_t hi, int steps, int64_t g_row0, int64_t height, bool omp,
-         const std::string& border) {
+         const std::string& border, int depth) {
         const Border bd = parse_border(border);
         const FrameLayout lay = FrameLayout::make(row_bytes, rows, halo);
         const HostView a = host_view(src, false), b = host_view(dst, true);
@@ -225,11 +227,11 @@ PYBIND11_MODULE(_pconv_native, m) {
         const Filter f = make_filter(filter);
         py::gil_scoped_release nogil;
         cpu_fused_launch(f, parse_channels(ch), lay, a.ptr, b.ptr, lo, hi, steps, g_row0, height,
-                         omp ? CpuBackend::OpenMP : CpuBackend::Serial, bd);
+                         omp ? CpuBackend::OpenMP : CpuBackend::Serial, bd, depth);
       },
       py::arg("filter"), py::arg("channels"), py::arg("row_bytes"), py::arg("rows"), py::arg("halo"), py::arg("src"),
       py::arg("dst"), py::arg("lo"), py::arg("hi"), py::arg("steps"), py::arg("g_row0"), py::arg("height"),
-      py::arg("omp") = false, py::arg("border") = "zero");
+      py::arg("omp") = false, py::arg("border") = "zero", py::arg("depth") = 8);
   m.def(
       "cpu_residual",
       [](py::buffer in, int64_t w, int64_t h, const std::string& ch, py::object filter, bool omp, int threads,
@@ -288,13 +290,14 @@ PYBIND11_MODULE(_pconv_native, m) {
   m.def("output_path_for", &output_path_for, py::arg("path"), py::arg("prefix") = "blur_");
   m.def(
       "read_raw",
-      [](const std::string& path, py::buffer dst, int64_t w, int64_t h, const std::string& ch) {
-        const ImageGeom g = make_geom(w, h, ch);
+      [](const std::string& path, py::buffer dst, int64_t w, int64_t h, const std::string& ch, int depth) {
+        const ImageGeom g = make_geom(w, h, ch, depth);
         const HostView b = host_view(dst, true);
         PCONV_CHECK(b.size == g.bytes(), "buffer size does not match the image geometry");
         read_image(path, g, b.ptr);
       },
-      py::arg("path"), py::arg("dst"), py::arg("width"), py::arg("height"), py::arg("channels"));
+      py::arg("path"), py::arg("dst"), py::arg("width"), py::arg("height"), py::arg("channels"),
+      py::arg("depth") = 8);
   m.def(
       "read_raw_rows",
       [](const std::string& path, py::buffer dst, int64_t w, int64_t h, const std::string& ch, int64_t y0,
@@ -309,13 +312,14 @@ PYBIND11_MODULE(_pconv_native, m) {
       py::arg("rows"));
   m.def(
       "write_raw",
-      [](const std::string& path, py::buffer src, int64_t w, int64_t h, const std::string& ch) {
-        const ImageGeom g = make_geom(w, h, ch);
+      [](const std::string& path, py::buffer src, int64_t w, int64_t h, const std::string& ch, int depth) {
+        const ImageGeom g = make_geom(w, h, ch, depth);
         const HostView b = host_view(src, false);
         PCONV_CHECK(b.size == g.bytes(), "buffer size does not match the image geometry");
         write_image(path, g, b.ptr);
       },
-      py::arg("path"), py::arg("src"), py::arg("width"), py::arg("height"), py::arg("channels"));
+      py::arg("path"), py::arg("src"), py::arg("width"), py::arg("height"), py::arg("channels"),
+      py::arg("depth") = 8);
   m.def(
       "create_output",
       [](const std::string& path, int64_t w, int64_t h, const std::string& ch) {
@@ -335,15 +339,16 @@ PYBIND11_MODULE(_pconv_native, m) {
       py::arg("rows"));
   m.def(
       "synth_rows",
-      [](py::buffer dst, int64_t w, int64_t h, const std::string& ch, uint64_t seed, int64_t y0, int64_t rows) {
-        const ImageGeom g = make_geom(w, h, ch);
+      [](py::buffer dst, int64_t w, int64_t h, const std::string& ch, uint64_t seed, int64_t y0, int64_t rows,
+         int depth) {
+        const ImageGeom g = make_geom(w, h, ch, depth);
         const HostView b = host_view(dst, true);
         PCONV_CHECK(b.size >= rows * g.row_bytes(), "buffer too small");
         py::gil_scoped_release nogil;
         synth_rows(g, seed, y0, rows, b.ptr, g.row_bytes());
       },
       py::arg("dst"), py::arg("width"), py::arg("height"), py::arg("channels"), py::arg("seed"), py::arg("y0"),
-      py::arg("rows"));
+      py::arg("rows"), py::arg("depth") = 8);
 
   // ---------------------------------------------------------------- CLI
   m.def("conv_main", [](std::vector<std::string> argv) {
@@ -446,10 +451,11 @@ PYBIND11_MODULE(_pconv_native, m) {
       [](py::object filter, const std::string& ch, uintptr_t src, uintptr_t dst, int64_t pitch, int64_t row_bytes,
          int64_t r0, int64_t r1, int64_t frame_lo, int64_t frame_hi, int steps, int64_t g_row0, int64_t height,
          uintptr_t stream, const std::string& variant, const std::string& border, int batch, int64_t batch_stride,
-         py::object dims, uintptr_t dims_ptr, py::object active, uintptr_t active_ptr, int batch_frames) {
+         py::object dims, uintptr_t dims_ptr, py::object active, uintptr_t active_ptr, int batch_frames, int depth) {
         StencilLaunch a;
         ImageSetArgs images;
         a.border = parse_border(border);
+        a.depth = depth;
         images.fill(a.images, batch, batch_stride, dims, dims_ptr, active, active_ptr, batch_frames);
         a.src = reinterpret_cast<const uint8_t*>(src);
         a.dst = reinterpret_cast<uint8_t*>(dst);
@@ -470,7 +476,7 @@ PYBIND11_MODULE(_pconv_native, m) {
       py::arg("g_row0") = 0, py::arg("height") = (int64_t(1) << 40), py::arg("stream") = 0,
       py::arg("variant") = "auto", py::arg("border") = "zero", py::arg("batch") = 1, py::arg("batch_stride") = 0,
       py::arg("dims") = py::none(), py::arg("dims_ptr") = 0, py::arg("active") = py::none(),
-      py::arg("active_ptr") = 0, py::arg("batch_frames") = 1);
+      py::arg("active_ptr") = 0, py::arg("batch_frames") = 1, py::arg("depth") = 8);
   m.def(
       "launch_residual",
       [](py::object filter, const std::string& ch, uintptr_t src, int64_t pitch, int64_t row_bytes, int64_t r0,
@@ -550,6 +556,19 @@ PYBIND11_MODULE(_pconv_native, m) {
     for (const auto& s : swar_shapes()) out.append(py::make_tuple(s.lw, s.m, s.nw));
     return out;
   });
+  m.def("set_swar16_shape", &set_swar16_shape, py::arg("lw") = 0, py::arg("m") = 0, py::arg("nw") = 0,
+        "Force the 16-bit temporal kernel's tile (lw samples per lane; lw=0: back to the pick / tuner).");
+  m.def("swar16_shapes", []() {
+    py::list out;
+    for (const auto& s : swar16_shapes()) out.append(py::make_tuple(s.lw, s.m, s.nw));
+    return out;
+  });
+  m.def("swar16_tuned", []() {
+    py::list out;
+    for (const auto& kv : swar16_tuned())
+      out.append(py::make_tuple(py::cast(kv.first), py::make_tuple(kv.second.lw, kv.second.m, kv.second.nw)));
+    return out;
+  });
   m.def(
       "swar_model",
       [](int steps, const std::string& ch, int64_t rows, int64_t row_bytes, int batch) {
@@ -606,10 +625,10 @@ PYBIND11_MODULE(_pconv_native, m) {
       },
       py::arg("steps"), py::arg("channels"), py::arg("rows"), py::arg("row_bytes"), py::arg("batch") = 1);
   m.def("auto_fuse",
-        [](py::object filter, const std::string& v, int64_t frame_bytes, int channels) {
-          return auto_fuse(make_filter(filter), parse_variant(v), frame_bytes, channels);
+        [](py::object filter, const std::string& v, int64_t frame_bytes, int channels, int depth) {
+          return auto_fuse(make_filter(filter), parse_variant(v), frame_bytes, channels, depth);
         },
-        py::arg("filter"), py::arg("variant"), py::arg("frame_bytes"), py::arg("channels") = 0,
+        py::arg("filter"), py::arg("variant"), py::arg("frame_bytes"), py::arg("channels") = 0, py::arg("depth") = 8,
         "Default repetitions per launch for a band frame of `frame_bytes` with `channels` bytes per pixel");
   m.def("supports_fusion",
         [](py::object filter, const std::string& v) { return supports_fusion(make_filter(filter), parse_variant(v)); },
@@ -646,7 +665,7 @@ PYBIND11_MODULE(_pconv_native, m) {
   py::class_<BandEngine>(m, "BandEngine")
       .def(py::init([](int64_t w, int64_t h, const std::string& ch, py::object filter, int rank, int world,
                        int device, int halo, int fuse, bool overlap, bool graph, const std::string& variant,
-                       bool kernel_copies, int stream_chunks, const std::string& border) {
+                       bool kernel_copies, int stream_chunks, const std::string& border, int depth) {
              EngineOptions o;
              o.border = parse_border(border);
              o.stream_chunks = stream_chunks;
@@ -657,13 +676,15 @@ PYBIND11_MODULE(_pconv_native, m) {
              o.overlap = overlap;
              o.use_graph = graph;
              o.variant = parse_variant(variant);
-             const ImageGeom g = make_geom(w, h, ch);
+             const ImageGeom g = make_geom(w, h, ch, depth);
              return std::make_unique<BandEngine>(g, row_band(h, world, rank), make_filter(filter), o);
            }),
            py::arg("width"), py::arg("height"), py::arg("channels"), py::arg("filter") = "gaussian",
            py::arg("rank") = 0, py::arg("world") = 1, py::arg("device") = 0, py::arg("halo") = 1, py::arg("fuse") = 1,
            py::arg("overlap") = true, py::arg("graph") = false, py::arg("variant") = "auto",
-           py::arg("kernel_copies") = false, py::arg("stream_chunks") = 0, py::arg("border") = "zero")
+           py::arg("kernel_copies") = false, py::arg("stream_chunks") = 0, py::arg("border") = "zero",
+           py::arg("depth") = 8)
+      .def_property_readonly("depth", [](const BandEngine& e) { return e.geom().depth; })
       .def_property_readonly("border", [](const BandEngine& e) { return std::string(border_name(e.options().border)); })
       .def_property_readonly("band", &BandEngine::band)
       .def("stream_plan", &BandEngine::stream_plan, py::arg("reps"), py::arg("in_r0"), py::arg("in_r1"))
@@ -786,7 +807,7 @@ PYBIND11_MODULE(_pconv_native, m) {
           "for_band",
           [](int64_t w, int64_t h, const std::string& ch, py::object filter, const Band& band, int device, int halo,
              int fuse, bool overlap, const std::string& variant, bool graph, bool capture_exchanges,
-             const std::string& border) {
+             const std::string& border, int depth) {
             // An explicit band (tests: e.g. a single rank whose up/down
             // neighbour is itself, to drive RCCL send/recv-to-self).
             EngineOptions o;
@@ -798,12 +819,12 @@ PYBIND11_MODULE(_pconv_native, m) {
             o.variant = parse_variant(variant);
             o.use_graph = graph;
             o.capture_exchanges = capture_exchanges;
-            return std::make_unique<BandEngine>(make_geom(w, h, ch), band, make_filter(filter), o);
+            return std::make_unique<BandEngine>(make_geom(w, h, ch, depth), band, make_filter(filter), o);
           },
           py::arg("width"), py::arg("height"), py::arg("channels"), py::arg("filter"), py::arg("band"),
           py::arg("device") = 0, py::arg("halo") = 1, py::arg("fuse") = 1, py::arg("overlap") = true,
           py::arg("variant") = "auto", py::arg("graph") = false, py::arg("capture_exchanges") = false,
-          py::arg("border") = "zero")
+          py::arg("border") = "zero", py::arg("depth") = 8)
       .def("set_stream_trace", &BandEngine::set_stream_trace, py::arg("on"),
            "diagnostics: time the next streamed images chunk by chunk (stream_trace())")
       .def("stream_trace", &BandEngine::stream_trace, py::call_guard<py::gil_scoped_release>(),
@@ -826,17 +847,18 @@ PYBIND11_MODULE(_pconv_native, m) {
   };
   py::class_<BatchEngine>(m, "BatchEngine")
       .def(py::init([](int64_t w, int64_t h, const std::string& ch, int capacity, py::object filter, int device,
-                       int fuse, const std::string& variant, const std::string& border) {
+                       int fuse, const std::string& variant, const std::string& border, int depth) {
              EngineOptions o;
              o.border = parse_border(border);
              o.device = device;
              o.fuse = fuse;
              o.variant = parse_variant(variant);
-             return std::make_unique<BatchEngine>(make_geom(w, h, ch), make_filter(filter), capacity, o);
+             return std::make_unique<BatchEngine>(make_geom(w, h, ch, depth), make_filter(filter), capacity, o);
            }),
            py::arg("width"), py::arg("height"), py::arg("channels"), py::arg("capacity"),
            py::arg("filter") = "gaussian", py::arg("device") = 0, py::arg("fuse") = 1, py::arg("variant") = "auto",
-           py::arg("border") = "zero")
+           py::arg("border") = "zero", py::arg("depth") = 8)
+      .def_property_readonly("depth", [](const BatchEngine& e) { return e.geom().depth; })
       .def_property_readonly("capacity", &BatchEngine::capacity)
       .def_property_readonly("border", [](const BatchEngine& e) { return std::string(border_name(e.options().border)); })
       .def_property_readonly("fuse", [](const BatchEngine& e) { return e.options().fuse; })

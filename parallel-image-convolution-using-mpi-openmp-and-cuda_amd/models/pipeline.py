@@ -53,8 +53,10 @@ class FilterPipeline:
     def apply(self, image, backend: str = "auto", device: Optional[int] = None, border: str = "zero"):
         """Run every stage in order (each under the same ``border`` rule); returns
         the same container type as ``image``."""
+        from ..ops.reference import refuse_depth16
         from ..ops.stencil import convolve
 
+        refuse_depth16(image, "FilterPipeline")
         out = image
         for s in self.stages:
             if s.reps:
@@ -63,8 +65,9 @@ class FilterPipeline:
 
     def reference(self, image, border: str = "zero"):
         """Independent NumPy oracle of the whole pipeline."""
-        from ..ops.reference import numpy_convolve
+        from ..ops.reference import numpy_convolve, refuse_depth16
 
+        refuse_depth16(image, "FilterPipeline")
         out = image
         for s in self.stages:
             out = numpy_convolve(out, s.reps, s.filter, border)

@@ -10,6 +10,11 @@ to the image (``border="replicate"``, ``np.pad(mode="edge")``), float32 multiply
 NumPy's float32 elementwise ops round each multiply and add separately (no FMA),
 which reproduces the reference bit for bit; integer-exact filters use
 ``(sum tap*p) >> shift`` directly.
+
+Depth 16: a ``uint16`` array stays ``uint16`` and runs the gaussian only, as
+``(sum tap*p) >> 4`` clamped at 65535 — which is what the reference's float32
+formula gives for 16-bit samples too (every product exact, every partial sum a
+multiple of 1/16 below 2^16).  Any other dtype is coerced to ``uint8`` as before.
 """
 from __future__ import annotations
 
@@ -34,19 +39,41 @@ def _as_hwc(img: np.ndarray) -> np.ndarray:
     raise ValueError("image must be (H, W) or (H, W, C)")
 
 
+def sample_dtype(img) -> np.dtype:
+    """``uint16`` for a ``uint16`` array (depth 16), else ``uint8``."""
+    return np.dtype(np.uint16) if getattr(img, "dtype", None) == np.uint16 else np.dtype(np.uint8)
+
+
+def refuse_depth16(image, what: str) -> None:
+    """The named error of everything that is not built for ``uint16`` images."""
+    if sample_dtype(image) == np.uint16 or str(getattr(image, "dtype", "")) == "torch.uint16":
+        raise ValueError(f"{what}: depth 16 (uint16 images) not supported")
+
+
+def check_depth16_filter(f) -> None:
+    """Depth 16 runs the gaussian only: every backend raises this error."""
+    g = get_filter("gaussian")
+    if (f.taps, f.divisor) != (g.taps, g.divisor):
+        raise ValueError(f"depth 16 (uint16 images) runs the gaussian filter only, not {f.name!r}")
+
+
 def numpy_step(img: np.ndarray, filt="gaussian", border: str = "zero") -> np.ndarray:
     f = get_filter(filt)
-    x = _as_hwc(np.asarray(img, dtype=np.uint8))
+    dt = sample_dtype(img)
+    if dt == np.uint16:
+        check_depth16_filter(f)
+    top = int(np.iinfo(dt).max)
+    x = _as_hwc(np.asarray(img, dtype=dt))
     h, w, _ = x.shape
     p = np.pad(x, ((1, 1), (1, 1), (0, 0)), mode="edge" if check_border(border) == "replicate" else "constant")
-    if f.int_exact:
+    if f.int_exact or dt == np.uint16:
         acc = np.zeros(x.shape, dtype=np.int64)
         for k in range(3):
             for l in range(3):
                 t = f.taps[3 * k + l]
                 if t:
                     acc += t * p[k : k + h, l : l + w].astype(np.int64)
-        out = np.minimum(acc >> f.shift, 255).astype(np.uint8)
+        out = np.minimum(acc >> f.shift, top).astype(dt)
     else:
         acc = np.zeros(x.shape, dtype=np.float32)
         w32 = f.weights32
@@ -61,7 +88,9 @@ def numpy_step(img: np.ndarray, filt="gaussian", border: str = "zero") -> np.nda
 
 def numpy_convolve(img: np.ndarray, reps: int = 1, filt="gaussian", border: str = "zero") -> np.ndarray:
     check_border(border)
-    out = np.asarray(img, dtype=np.uint8).copy()
+    out = np.asarray(img, dtype=sample_dtype(img)).copy()
+    if out.dtype == np.uint16:
+        check_depth16_filter(get_filter(filt))
     for _ in range(int(reps)):
         out = numpy_step(out, filt, border)
     return out
@@ -71,5 +100,7 @@ def numpy_residual(img: np.ndarray, filt="gaussian", border: str = "zero") -> in
     """Bytes of ``img`` that one more repetition would change; 0 means ``img``
     is a fixed point of the iterated map.  By definition
     ``count_nonzero(numpy_convolve(img, 1, filt, border) != img)``."""
+    if sample_dtype(img) == np.uint16:
+        raise ValueError("residual: depth 16 (uint16 images) not supported")
     x = np.asarray(img, dtype=np.uint8)
     return int(np.count_nonzero(numpy_convolve(x, 1, filt, border) != x))

@@ -25,9 +25,53 @@ import torch
 
 from .._native import require_native
 from ..models.filters import get_filter
-from .reference import check_border, numpy_convolve, numpy_residual, numpy_step
+from .reference import check_border, check_depth16_filter, numpy_convolve, numpy_residual, numpy_step
 
 _CHANNELS = {1: "grey", 3: "rgb", 4: "rgba"}
+_CH_COUNT = {"grey": 1, "rgb": 3, "rgba": 4}
+_NP_DTYPE = {8: np.uint8, 16: np.uint16}
+_TORCH_DTYPE = {8: torch.uint8, 16: torch.uint16}
+
+
+def image_depth(image) -> int:
+    """Bits per sample an image selects: 16 for dtype ``uint16`` (NumPy or
+    ``torch.uint16``), 8 for everything else."""
+    return 16 if getattr(image, "dtype", None) in (np.uint16, torch.uint16) else 8
+
+
+def _check_tensor_dtype(image) -> None:
+    if isinstance(image, torch.Tensor) and image.dtype not in (torch.uint8, torch.uint16):
+        raise TypeError("image tensor must be uint8 (or uint16 for depth 16)")
+
+
+def _check_depth(depth: int, flt, variant: str = "auto", graph: bool = False) -> int:
+    """What depth 16 runs: the gaussian on the auto / temporal kernel, no graph replay."""
+    if depth not in (8, 16):
+        raise ValueError(f"depth must be 8 or 16, got {depth!r}")
+    if depth == 16:
+        check_depth16_filter(flt)
+        if variant not in ("auto", "temporal"):
+            raise ValueError(f"depth 16 (uint16 images) not supported by kernel {variant!r} (auto|temporal only)")
+        if graph:
+            raise ValueError("depth 16 (uint16 images) not supported with graph=True")
+    return depth
+
+
+def _refuse_depth16(image, what: str) -> None:
+    if image_depth(image) == 16:
+        raise ValueError(f"{what}: depth 16 (uint16 images) not supported")
+
+
+def _host_samples(image, depth: int) -> np.ndarray:
+    """``image`` (array or tensor) as a C-contiguous host array of the depth's dtype."""
+    if isinstance(image, torch.Tensor):
+        image = image.cpu().numpy()
+    return np.ascontiguousarray(image, dtype=_NP_DTYPE[depth])
+
+
+def _bytes_of(arr: np.ndarray) -> np.ndarray:
+    """The flat byte view the native bindings take."""
+    return arr.reshape(-1).view(np.uint8)
 
 
 def image_geometry(shape) -> Tuple[int, int, str]:
@@ -86,19 +130,21 @@ class Engine:
     """
 
     def __init__(self, width: int, height: int, channels: str = "grey", filter="gaussian", device: int = 0,
-                 fuse: Optional[int] = None, graph: bool = False, variant: str = "auto", border: str = "zero"):
+                 fuse: Optional[int] = None, graph: bool = False, variant: str = "auto", border: str = "zero",
+                 depth: int = 8):
         n = require_native()
         self.border = check_border(border)
         self.filter = get_filter(filter)
+        self.depth = _check_depth(int(depth), self.filter, variant, graph)
         nf = self.filter.to_native()
         if fuse is None:
-            ch = {"grey": 1, "rgb": 3, "rgba": 4}[channels]
-            fuse = n.auto_fuse(nf, variant, int(width) * int(height) * ch, ch)
+            ch = _CH_COUNT[channels]
+            fuse = n.auto_fuse(nf, variant, int(width) * int(height) * ch * (self.depth // 8), ch, depth=self.depth)
         self.width, self.height, self.channels = int(width), int(height), channels
         self.device = int(device)
         self._eng = n.BandEngine(self.width, self.height, channels, nf, 0, 1, self.device, halo=int(fuse),
                                  fuse=int(fuse), overlap=True, graph=bool(graph), variant=variant,
-                                 border=self.border)
+                                 border=self.border, depth=self.depth)
         self.row_bytes = self._eng.row_bytes
 
     @property
@@ -112,16 +158,24 @@ class Engine:
     def plan(self, reps: int):
         return self._eng.plan(reps)
 
+    def _check_samples(self, img) -> None:
+        """A uint16 image on a depth-8 engine would be wrapped modulo 256, a
+        device tensor of the other width misread: both are errors."""
+        if image_depth(img) != self.depth and (self.depth == 8 or isinstance(img, torch.Tensor)):
+            raise TypeError(f"engine of depth {self.depth} got a {img.dtype} image")
+
     def run_numpy(self, img: np.ndarray, reps: int) -> np.ndarray:
-        src = np.ascontiguousarray(img, dtype=np.uint8)
+        self._check_samples(img)
+        src = _host_samples(img, self.depth)
         out = np.empty_like(src)
-        self._eng.upload(src.reshape(-1), 0, self.height)
+        self._eng.upload(_bytes_of(src), 0, self.height)
         self._eng.run(int(reps))
-        self._eng.download(out.reshape(-1), 0, self.height)
+        self._eng.download(_bytes_of(out), 0, self.height)
         self._eng.synchronize()
         return out
 
     def run_tensor(self, t: torch.Tensor, reps: int) -> torch.Tensor:
+        self._check_samples(t)
         if t.device.type != "cuda":
             return torch.from_numpy(self.run_numpy(t.numpy(), reps))
         src = t.contiguous()
@@ -144,6 +198,9 @@ class Engine:
     def _with_frame(self, img, work):
         """Upload ``img`` (array or tensor), ``work()`` on the resident frame,
         download the newest frame into the input's container type."""
+        _refuse_depth16(img, "residual / run_until_stable")
+        if self.depth == 16:
+            raise ValueError("residual / run_until_stable: depth 16 not supported")
         if isinstance(img, torch.Tensor) and img.device.type == "cuda":
             src = img.contiguous()
             out = torch.empty_like(src)
@@ -168,6 +225,8 @@ class Engine:
         """Bytes one more repetition would change: of ``img``, or (``None``) of
         the frame the engine holds after its last run."""
         if img is None:
+            if self.depth == 16:
+                raise ValueError("residual: depth 16 not supported")
             return int(self._eng.residual())
         return int(self._with_frame(img, self._eng.residual)[1])
 
@@ -186,11 +245,12 @@ _ENGINES: "OrderedDict[tuple, Engine]" = OrderedDict()
 _MAX_CACHED = 8
 
 
-def _cached_engine(w, h, ch, flt, device, fuse, graph, variant, border="zero") -> Engine:
-    key = (w, h, ch, flt.taps, flt.divisor, device, fuse, graph, variant, border)
+def _cached_engine(w, h, ch, flt, device, fuse, graph, variant, border="zero", depth=8) -> Engine:
+    key = (w, h, ch, flt.taps, flt.divisor, device, fuse, graph, variant, border, depth)
     eng = _ENGINES.get(key)
     if eng is None:
-        eng = Engine(w, h, ch, flt, device=device, fuse=fuse, graph=graph, variant=variant, border=border)
+        eng = Engine(w, h, ch, flt, device=device, fuse=fuse, graph=graph, variant=variant, border=border,
+                     depth=depth)
         _ENGINES[key] = eng
         while len(_ENGINES) > _MAX_CACHED:
             _ENGINES.popitem(last=False)
@@ -210,7 +270,8 @@ def _default_backend() -> str:
 def convolve(image, reps: int = 1, filter="gaussian", backend: str = "auto", device: Optional[int] = None,
              fuse: Optional[int] = None, graph: bool = False, variant: str = "auto", threads: int = 0,
              border: str = "zero"):
-    """Apply ``reps`` 3x3 convolutions to an 8-bit image.
+    """Apply ``reps`` 3x3 convolutions to an 8-bit image, or (dtype ``uint16``,
+    NumPy or ``torch.uint16``: depth 16, the gaussian only) to a 16-bit one.
 
     ``border``: what a tap reads outside the image — ``"zero"`` (default, the
     reference's zero padding) or ``"replicate"`` (the nearest image pixel: no
@@ -224,11 +285,14 @@ def convolve(image, reps: int = 1, filter="gaussian", backend: str = "auto", dev
     flt = get_filter(filter)
     check_border(border)
     is_tensor = isinstance(image, torch.Tensor)
-    if is_tensor and image.dtype != torch.uint8:
-        raise TypeError("image tensor must be uint8")
+    _check_tensor_dtype(image)
+    depth = image_depth(image)
     w, h, ch = image_geometry(tuple(image.shape))
     if backend == "auto":
         backend = "hip" if (is_tensor and image.is_cuda) else _default_backend()
+    if backend not in ("numpy", "cpu", "omp", "hip"):
+        raise ValueError(f"unknown backend {backend!r} (hip|omp|cpu|numpy|auto)")
+    _check_depth(depth, flt, variant if backend == "hip" else "auto", graph and backend == "hip")
 
     if backend == "numpy":
         arr = image.cpu().numpy() if is_tensor else np.asarray(image)
@@ -237,16 +301,16 @@ def convolve(image, reps: int = 1, filter="gaussian", backend: str = "auto", dev
 
     if backend in ("cpu", "omp"):
         n = require_native()
-        arr = np.ascontiguousarray(image.cpu().numpy() if is_tensor else image, dtype=np.uint8)
+        arr = _host_samples(image, depth)
         out = np.empty_like(arr)
-        n.cpu_convolve(arr.reshape(-1), out.reshape(-1), w, h, ch, int(reps), flt.to_native(), backend == "omp",
-                       int(threads), border=border)
+        n.cpu_convolve(_bytes_of(arr), _bytes_of(out), w, h, ch, int(reps), flt.to_native(), backend == "omp",
+                       int(threads), border=border, depth=depth)
         return torch.from_numpy(out).to(image.device) if is_tensor else out
 
     if backend == "hip":
         if device is None:
             device = image.device.index if (is_tensor and image.is_cuda) else 0
-        eng = _cached_engine(w, h, ch, flt, int(device or 0), fuse, graph, variant, border)
+        eng = _cached_engine(w, h, ch, flt, int(device or 0), fuse, graph, variant, border, depth)
         return eng(image, reps)
 
     raise ValueError(f"unknown backend {backend!r} (hip|omp|cpu|numpy|auto)")
@@ -268,6 +332,7 @@ def residual(image, filter="gaussian", backend: str = "auto", device: Optional[i
     flt = get_filter(filter)
     check_border(border)
     is_tensor = isinstance(image, torch.Tensor)
+    _refuse_depth16(image, "residual")
     if is_tensor and image.dtype != torch.uint8:
         raise TypeError("image tensor must be uint8")
     w, h, ch = image_geometry(tuple(image.shape))
@@ -299,6 +364,7 @@ def convolve_until_stable(image, max_reps: int, filter="gaussian", check_every: 
     flt = get_filter(filter)
     check_border(border)
     is_tensor = isinstance(image, torch.Tensor)
+    _refuse_depth16(image, "convolve_until_stable")
     if is_tensor and image.dtype != torch.uint8:
         raise TypeError("image tensor must be uint8")
     w, h, ch = image_geometry(tuple(image.shape))
@@ -353,18 +419,20 @@ class BatchEngine:
     """
 
     def __init__(self, width: int, height: int, channels: str = "grey", capacity: int = 1, filter="gaussian",
-                 device: int = 0, fuse: Optional[int] = None, variant: str = "auto", border: str = "zero"):
+                 device: int = 0, fuse: Optional[int] = None, variant: str = "auto", border: str = "zero",
+                 depth: int = 8):
         n = require_native()
         self.border = check_border(border)
         self.filter = get_filter(filter)
+        self.depth = _check_depth(int(depth), self.filter, variant)
         nf = self.filter.to_native()
         if fuse is None:
-            ch = {"grey": 1, "rgb": 3, "rgba": 4}[channels]
-            fuse = n.auto_fuse(nf, variant, int(width) * int(height) * ch, ch)
+            ch = _CH_COUNT[channels]
+            fuse = n.auto_fuse(nf, variant, int(width) * int(height) * ch * (self.depth // 8), ch, depth=self.depth)
         self.width, self.height, self.channels = int(width), int(height), channels
         self.device = int(device)
         self._eng = n.BatchEngine(self.width, self.height, channels, int(capacity), nf, self.device, fuse=int(fuse),
-                                  variant=variant, border=self.border)
+                                  variant=variant, border=self.border, depth=self.depth)
         self.capacity = self._eng.capacity
         self.row_bytes = self._eng.row_bytes
         self._n = 0  # images of the last call (residual(None) counts those)
@@ -386,7 +454,7 @@ class BatchEngine:
         return shape[0]
 
     def _transfer(self, flat, n: int, work, sizes=None):
-        """The bracket every call shares.  ``flat``: the packed bytes of ``n``
+        """The bracket every call shares.  ``flat``: the packed samples of ``n``
         images, a 1-D NumPy array or CUDA tensor (which never leaves the
         device); ``sizes``: their ``[(width, height)]``, or ``None`` for images
         of the engine's geometry.  Waits for the caller's stream, uploads,
@@ -404,9 +472,10 @@ class BatchEngine:
         if device:
             ts = torch.cuda.current_stream(flat.device).cuda_stream
             e.wait_stream(ts)
-        getattr(e, "upload" + form)(flat.data_ptr() if device else flat, n if sizes is None else sizes, **kw)
+        getattr(e, "upload" + form)(flat.data_ptr() if device else _bytes_of(flat), n if sizes is None else sizes, **kw)
         res = work(n)
-        getattr(e, "download" + form)(out.data_ptr() if device else out, *([n] if sizes is None else []), **kw)
+        getattr(e, "download" + form)(out.data_ptr() if device else _bytes_of(out), *([n] if sizes is None else []),
+                                      **kw)
         if device:
             e.signal_stream(ts)
             flat.record_stream(torch.cuda.current_stream(flat.device))
@@ -419,11 +488,17 @@ class BatchEngine:
         work's result)``."""
         is_tensor = isinstance(stack, torch.Tensor)
         on_gpu = is_tensor and stack.device.type == "cuda"
-        src = stack.contiguous() if on_gpu else np.ascontiguousarray(stack.numpy() if is_tensor else stack,
-                                                                     dtype=np.uint8)
+        self._check_samples(stack)
+        src = stack.contiguous() if on_gpu else _host_samples(stack, self.depth)
         out, res = self._transfer(src.reshape(-1), self._check_stack(src.shape), work)
         out = out.reshape(src.shape)
         return (torch.from_numpy(out) if is_tensor and not on_gpu else out), res
+
+    _check_samples = Engine._check_samples
+
+    def _refuse_depth16(self, what: str) -> None:
+        if self.depth == 16:
+            raise ValueError(f"{what}: depth 16 not supported")
 
     def run_numpy(self, stack: np.ndarray, reps: int) -> np.ndarray:
         return self._with_frames(np.asarray(stack), lambda n: self._eng.run(int(reps), n))[0]
@@ -438,6 +513,7 @@ class BatchEngine:
 
     # ---- fixed points ------------------------------------------------
     def _residual(self, images, bracket) -> np.ndarray:
+        self._refuse_depth16("residual")
         if images is None:
             res = self._eng.residual(self._n) if self._n else []
         else:
@@ -445,6 +521,7 @@ class BatchEngine:
         return np.asarray(res, dtype=np.int64).reshape(-1)
 
     def _until_stable(self, images, bracket, max_reps, check_every, compact):
+        self._refuse_depth16("run_until_stable")
         max_reps, k = _check_stable_args(max_reps, check_every)
         if k is None:
             k = _GPU_CHECK_LAUNCHES * self.fuse
@@ -493,11 +570,13 @@ class BatchEngine:
         seq, sizes = self._check_images(images)
         tensors = [isinstance(im, torch.Tensor) for im in seq]
         on_gpu = bool(seq) and all(tensors) and all(im.device.type == "cuda" for im in seq)
+        for im in seq:
+            self._check_samples(im)
         if on_gpu:
             flat = torch.cat([im.contiguous().reshape(-1) for im in seq])
         else:
-            flat = np.concatenate([np.ascontiguousarray(im.cpu().numpy() if t else im, dtype=np.uint8).reshape(-1)
-                                   for im, t in zip(seq, tensors)] or [np.empty(0, np.uint8)])
+            flat = np.concatenate([_host_samples(im, self.depth).reshape(-1) for im in seq]
+                                  or [np.empty(0, _NP_DTYPE[self.depth])])
         out, res = self._transfer(flat, len(seq), work, sizes)
         outs, at = [], 0
         for im, t in zip(seq, tensors):
@@ -536,37 +615,39 @@ _MAX_CACHED_BATCH = 2
 _BATCH_BYTES = 1 << 30
 
 
-def _cached_batch_engine(w, h, ch, capacity, flt, device, fuse, variant, border) -> BatchEngine:
-    key = (w, h, ch, capacity, flt.taps, flt.divisor, device, fuse, variant, border)
+def _cached_batch_engine(w, h, ch, capacity, flt, device, fuse, variant, border, depth=8) -> BatchEngine:
+    key = (w, h, ch, capacity, flt.taps, flt.divisor, device, fuse, variant, border, depth)
     eng = _BATCH_ENGINES.get(key)
     if eng is None:
         # make room first: two engines of the memory bound are the cache's most
         while len(_BATCH_ENGINES) >= _MAX_CACHED_BATCH:
             _BATCH_ENGINES.popitem(last=False)
-        eng = BatchEngine(w, h, ch, capacity, flt, device=device, fuse=fuse, variant=variant, border=border)
+        eng = BatchEngine(w, h, ch, capacity, flt, device=device, fuse=fuse, variant=variant, border=border,
+                          depth=depth)
         _BATCH_ENGINES[key] = eng
     else:
         _BATCH_ENGINES.move_to_end(key)
     return eng
 
 
-def _frame_bytes(w: int, h: int, ch: str, fuse: int) -> int:
+def _frame_bytes(w: int, h: int, ch: str, fuse: int, depth: int = 8) -> int:
     """Bytes of one device frame (csrc/include/pconv/image.hpp, FrameLayout):
     16 pad bytes, the row, at least 32 more, rounded to 128; ``fuse`` ghost
     rows above and below."""
-    row_bytes = w * {"grey": 1, "rgb": 3, "rgba": 4}[ch]
-    pitch = -(-(16 + row_bytes + 32) // 128) * 128
+    row_bytes = w * _CH_COUNT[ch] * (depth // 8)
+    pitch = -(-(16 + -(-row_bytes // 16) * 16 + 32) // 128) * 128
     return pitch * (h + 2 * fuse)
 
 
 def _as_stack(images):
-    """``images`` as one uint8 stack ``(N, H, W[, C])``; (stack, is_tensor)."""
+    """``images`` as one uint8 (or uint16: depth 16) stack ``(N, H, W[, C])``;
+    (stack, is_tensor)."""
     if isinstance(images, torch.Tensor):
-        if images.dtype != torch.uint8:
+        if images.dtype not in (torch.uint8, torch.uint16):
             raise TypeError("image tensor must be uint8")
         return images, True
     if isinstance(images, np.ndarray):
-        if images.dtype != np.uint8:
+        if images.dtype not in (np.uint8, np.uint16):
             raise TypeError("image array must be uint8")
         return images, False
     seq = list(images)
@@ -576,11 +657,11 @@ def _as_stack(images):
     if len(shapes) != 1:
         raise ValueError(f"images of a batch must have one shape, got {sorted(shapes)}")
     if all(isinstance(im, torch.Tensor) for im in seq):
-        if any(im.dtype != torch.uint8 for im in seq):
+        if any(im.dtype != seq[0].dtype or im.dtype not in (torch.uint8, torch.uint16) for im in seq):
             raise TypeError("image tensor must be uint8")
         return torch.stack(seq), True
     arrs = [im.cpu().numpy() if isinstance(im, torch.Tensor) else np.asarray(im) for im in seq]
-    if any(a.dtype != np.uint8 for a in arrs):
+    if any(a.dtype != arrs[0].dtype or a.dtype not in (np.uint8, np.uint16) for a in arrs):
         raise TypeError("image array must be uint8")
     return np.stack(arrs), False
 
@@ -605,7 +686,7 @@ def _prepare_batch(images, filter, backend, border, batch_size):
 
 
 def _empty_like_stack(stack, is_tensor):
-    return torch.empty_like(stack) if is_tensor else np.empty(tuple(stack.shape), dtype=np.uint8)
+    return torch.empty_like(stack) if is_tensor else np.empty(tuple(stack.shape), dtype=stack.dtype)
 
 
 def _hip_batch_engine(stack, is_tensor, geo, flt, device, fuse, variant, border, batch_size):
@@ -616,15 +697,16 @@ def _hip_batch_engine(stack, is_tensor, geo, flt, device, fuse, variant, border,
     if device is None:
         device = stack.device.index if (is_tensor and stack.is_cuda) else 0
     device = int(device or 0)
+    depth = _check_depth(image_depth(stack), flt, variant)
     if fuse is None:
-        c = {"grey": 1, "rgb": 3, "rgba": 4}[ch]
-        fuse = n.auto_fuse(flt.to_native(), variant, w * h * c, c)
+        c = _CH_COUNT[ch]
+        fuse = n.auto_fuse(flt.to_native(), variant, w * h * c * (depth // 8), c, depth=depth)
     fuse = int(fuse)
     if batch_size is None:
-        cap = max(1, min(n_img, _BATCH_BYTES // (2 * _frame_bytes(w, h, ch, fuse))))
+        cap = max(1, min(n_img, _BATCH_BYTES // (2 * _frame_bytes(w, h, ch, fuse, depth))))
     else:
         cap = min(n_img, int(batch_size))
-    return _cached_batch_engine(w, h, ch, cap, flt, device, fuse, variant, border), cap
+    return _cached_batch_engine(w, h, ch, cap, flt, device, fuse, variant, border, depth), cap
 
 
 def convolve_batch(images, reps: int = 1, filter="gaussian", backend: str = "auto", device: Optional[int] = None,
@@ -647,6 +729,7 @@ def convolve_batch(images, reps: int = 1, filter="gaussian", backend: str = "aut
     if reps < 0:
         raise ValueError("reps must be >= 0")
     flt, stack, is_tensor, geo, backend = _prepare_batch(images, filter, backend, border, batch_size)
+    _check_depth(image_depth(stack), flt, variant if backend == "hip" else "auto")
     n_img = int(stack.shape[0])
     if n_img == 0:
         return _empty_like_stack(stack, is_tensor)
@@ -686,6 +769,7 @@ def convolve_batch_until_stable(images, max_reps: int, filter="gaussian", check_
     """
     _check_stable_args(max_reps, check_every)
     flt, stack, is_tensor, geo, backend = _prepare_batch(images, filter, backend, border, batch_size)
+    _refuse_depth16(stack, "convolve_batch_until_stable")
     n_img = int(stack.shape[0])
     if n_img == 0:
         return _empty_like_stack(stack, is_tensor), []
@@ -711,6 +795,7 @@ def residual_batch(images, filter="gaussian", backend: str = "auto", device: Opt
     ``[residual(img, ...) for img in images]``; on the ``hip`` backend one
     launch of the residual kernel per chunk of the batch engine."""
     flt, stack, is_tensor, geo, backend = _prepare_batch(images, filter, backend, border, None)
+    _refuse_depth16(stack, "residual_batch")
     n_img = int(stack.shape[0])
     if n_img == 0:
         return np.zeros((0,), dtype=np.int64)
@@ -723,11 +808,8 @@ def residual_batch(images, filter="gaussian", backend: str = "auto", device: Opt
 
 # ---- images of different sizes ------------------------------------------------
 
-_CH_COUNT = {"grey": 1, "rgb": 3, "rgba": 4}
-
-
 def size_buckets(sizes, channels, fuse, min_fill: float = 0.5, batch_size: Optional[int] = None,
-                 max_bytes: int = _BATCH_BYTES):
+                 max_bytes: int = _BATCH_BYTES, depth: int = 8):
     """Group images of different sizes into envelopes for :class:`BatchEngine`.
 
     ``sizes``: ``[(width, height)]``; ``channels``: ``"grey" | "rgb" | "rgba"``
@@ -745,7 +827,8 @@ def size_buckets(sizes, channels, fuse, min_fill: float = 0.5, batch_size: Optio
 
     ``min_fill = 0.5`` is a waste policy (at most half of a bucket's tile work
     and frame memory goes to area outside its images), like the 1 GiB of
-    ``max_bytes``: neither is a tuned number.
+    ``max_bytes``: neither is a tuned number.  ``depth``: bits per sample
+    (8 | 16) of the frames the bytes are counted for.
     """
     ch = _CHANNELS[channels] if channels in _CHANNELS else channels
     if ch not in _CH_COUNT:
@@ -768,7 +851,7 @@ def size_buckets(sizes, channels, fuse, min_fill: float = 0.5, batch_size: Optio
             e = (max(env[0], w), max(env[1], h))
             fits = ((area + w * h) >= float(min_fill) * n * e[0] * e[1]
                     and (batch_size is None or n <= int(batch_size))
-                    and 2 * n * _frame_bytes(e[0], e[1], ch, fuse_of(*e)) <= max_bytes)
+                    and 2 * n * _frame_bytes(e[0], e[1], ch, fuse_of(*e), depth) <= max_bytes)
             if fits:
                 members.append(i)
                 env, area = e, area + w * h
@@ -800,7 +883,8 @@ def _prepare_many(images, filter, backend, border, batch_size, min_fill):
     if len(kinds) != 1 or not all(isinstance(im, (torch.Tensor, np.ndarray)) for im in seq):
         raise TypeError("images must be all NumPy arrays or all torch tensors")
     is_tensor = kinds.pop()
-    if any(im.dtype != (torch.uint8 if is_tensor else np.uint8) for im in seq):
+    ok = (torch.uint8, torch.uint16) if is_tensor else (np.uint8, np.uint16)
+    if any(im.dtype != seq[0].dtype or im.dtype not in ok for im in seq):
         raise TypeError("image tensor must be uint8" if is_tensor else "image array must be uint8")
     chans = {image_geometry(tuple(im.shape))[2] for im in seq}
     if len(chans) != 1:
@@ -822,10 +906,12 @@ def _hip_buckets(seq, is_tensor, ch, flt, device, fuse, variant, border, batch_s
     device = int(device or 0)
     c = _CH_COUNT[ch]
     nf = flt.to_native()
-    fuse_of = (lambda w, h: int(n.auto_fuse(nf, variant, w * h * c, c))) if fuse is None else (lambda w, h: int(fuse))
+    depth = _check_depth(image_depth(seq[0]), flt, variant)
+    fuse_of = ((lambda w, h: int(n.auto_fuse(nf, variant, w * h * c * (depth // 8), c, depth=depth)))
+               if fuse is None else (lambda w, h: int(fuse)))
     sizes = [image_geometry(tuple(im.shape))[:2] for im in seq]
-    for (w, h), idx in size_buckets(sizes, ch, fuse_of, min_fill, batch_size):
-        yield _cached_batch_engine(w, h, ch, len(idx), flt, device, fuse_of(w, h), variant, border), idx
+    for (w, h), idx in size_buckets(sizes, ch, fuse_of, min_fill, batch_size, depth=depth):
+        yield _cached_batch_engine(w, h, ch, len(idx), flt, device, fuse_of(w, h), variant, border, depth), idx
 
 
 def convolve_many(images, reps: int = 1, filter="gaussian", backend: str = "auto", device: Optional[int] = None,
@@ -849,6 +935,7 @@ def convolve_many(images, reps: int = 1, filter="gaussian", backend: str = "auto
     flt, seq, is_tensor, ch, backend = _prepare_many(images, filter, backend, border, batch_size, min_fill)
     if not seq:
         return []
+    _check_depth(image_depth(seq[0]), flt, variant if backend == "hip" else "auto")
     if backend != "hip":
         return [convolve(im, reps, flt, backend=backend, threads=threads, border=border) for im in seq]
     outs = [None] * len(seq)
@@ -874,6 +961,7 @@ def convolve_many_until_stable(images, max_reps: int, filter="gaussian", check_e
     flt, seq, is_tensor, ch, backend = _prepare_many(images, filter, backend, border, batch_size, min_fill)
     if not seq:
         return [], []
+    _refuse_depth16(seq[0], "convolve_many_until_stable")
     if backend != "hip":
         res = [convolve_until_stable(im, max_reps, flt, check_every=check_every, backend=backend, threads=threads,
                                      border=border) for im in seq]
@@ -894,6 +982,7 @@ def residual_many(images, filter="gaussian", backend: str = "auto", device: Opti
     flt, seq, is_tensor, ch, backend = _prepare_many(images, filter, backend, border, batch_size, min_fill)
     if not seq:
         return np.zeros((0,), dtype=np.int64)
+    _refuse_depth16(seq[0], "residual_many")
     if backend != "hip":
         return np.asarray([residual(im, flt, backend=backend, threads=threads, border=border) for im in seq],
                           dtype=np.int64)
@@ -905,13 +994,13 @@ def residual_many(images, filter="gaussian", backend: str = "auto", device: Opti
 
 def convolve_file(path: str, width: int, height: int, reps: int, channels: str = "grey", filter="gaussian",
                   out: Optional[str] = None, backend: str = "auto", device: Optional[int] = None,
-                  border: str = "zero") -> str:
+                  border: str = "zero", depth: int = 8) -> str:
     """The reference program in one call (``cuda/main.c:10-53``): read the raw
     image, ``reps`` repetitions, write ``blur_<name>`` (or ``out``); returns the
     output path."""
     from ..utils.raw_io import output_path_for, read_raw, write_raw
 
-    img = read_raw(path, width, height, channels)
+    img = read_raw(path, width, height, channels, depth=depth)
     res = convolve(img, reps, filter, backend=backend, device=device, border=border)
     dst = out or output_path_for(path)
     write_raw(dst, res)

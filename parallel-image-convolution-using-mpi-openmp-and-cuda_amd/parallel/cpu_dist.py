@@ -19,6 +19,7 @@ import torch.distributed as dist
 
 from .._native import require_native
 from ..models.filters import get_filter
+from ..ops.reference import refuse_depth16
 
 
 class CpuBandRunner:
@@ -101,6 +102,7 @@ def local_cpu_cluster_convolve(image: np.ndarray, reps: int, world: int, filter=
                                channels: Optional[str] = None, border: str = "zero") -> np.ndarray:
     """All `world` bands in this process, halos copied between NumPy frames —
     the CPU twin of the native one-device ``LocalCluster``."""
+    refuse_depth16(image, "local_cpu_cluster_convolve")
     img = np.ascontiguousarray(image, dtype=np.uint8)
     h, w = img.shape[:2]
     if channels is None:
@@ -150,6 +152,7 @@ def distributed_cpu_convolve(image: np.ndarray, reps: int, filter="gaussian", *,
     (bands gathered with all_gather)."""
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     world = dist.get_world_size(group) if dist.is_initialized() else 1
+    refuse_depth16(image, "distributed_cpu_convolve")
     img = np.ascontiguousarray(image, dtype=np.uint8)
     h, w = img.shape[:2]
     if channels is None:

@@ -19,6 +19,7 @@ import numpy as np
 
 from .._native import require_native
 from ..models.filters import get_filter
+from ..ops.reference import refuse_depth16
 from .bootstrap import env_context, make_rccl_comm
 
 AUTO_HALO_CAP = 64
@@ -319,6 +320,7 @@ class DistributedBlur:
                 n.flush_host_cache(self._in[i].ptr, len(self._in[i]))
 
     def load_image(self, image: np.ndarray, slot: Optional[int] = None) -> None:
+        refuse_depth16(image, "DistributedBlur")
         self._quiesce()
         a, b = self.input_rows
         rows = np.ascontiguousarray(image, dtype=np.uint8).reshape(self.height, self.row_bytes)[a:b]
