@@ -218,6 +218,8 @@ void clear_float_tuning();
 // tile kernel k_swar, 1: the buffer-op tile kernel k_swar_pf; live: the workgroups of a mixed-size launch
 // (ImageSet::dims) that have output in their image, 0 for a uniform launch.
 std::vector<std::pair<std::vector<int64_t>, SwarShape>> swar_tuned();
+// Tuned float entries: ({channels, uniform, steps, rows, row_bytes, batch, live}, shape); uniform 1: nine equal taps.
+std::vector<std::pair<std::vector<int64_t>, FloatShape>> float_tuned();
 
 // The 16-bit gaussian kernel's family (kernels/stencil_swar16.hip): lw is the
 // SAMPLES per lane (4 or 8: 8- or 16-byte lane loads), one column strip per

@@ -647,4 +647,14 @@ void clear_float_tuning() {
   g_ft_tuned.clear();
 }
 
+std::vector<std::pair<std::vector<int64_t>, FloatShape>> float_tuned() {
+  std::lock_guard<std::mutex> lk(g_ft_mu);
+  std::vector<std::pair<std::vector<int64_t>, FloatShape>> out;
+  for (const auto& kv : g_ft_tuned)
+    out.push_back({{kv.first.ch, kv.first.uniform ? 1 : 0, kv.first.steps, kv.first.rows, kv.first.row_bytes,
+                    kv.first.batch, kv.first.live},
+                   kv.second});
+  return out;
+}
+
 }  // namespace pconv

@@ -741,6 +741,12 @@ SwarChoice tuned_choice(const StencilLaunch& a, Channels ch, hipStream_t stream,
     if (it != g_tuned.end()) {
       SwarChoice r = it->second;
       if (mode >= 0) r.form = mode;  // forced form (the shape stays tuned)
+      // The key leaves out what the buffer-op kernel's rule reads: the pitch,
+      // the row-byte residues of a dims table, the frames an active table
+      // names; and set_prefetch_mode may have changed since.  A launch the rule
+      // refuses runs the entry's shape and form on the tile kernel (every
+      // buffer-op shape is a row of the same table); the entry stays.
+      if (r.kern == 1 && !(pf_mode() != 0 && pf_launch_ok(a, a.steps))) r.kern = 0;
       return r;
     }
   }

@@ -600,6 +600,12 @@ PYBIND11_MODULE(_pconv_native, m) {
     for (const auto& s : float_shapes()) out.append(py::make_tuple(s.m, s.nw));
     return out;
   });
+  m.def("float_tuned", []() {
+    py::list out;
+    for (const auto& kv : float_tuned())
+      out.append(py::make_tuple(py::cast(kv.first), py::make_tuple(kv.second.m, kv.second.nw)));
+    return out;
+  });
   m.def("swar_prefetch_shapes", []() {
     py::list out;
     for (const auto& s : swar_prefetch_shapes()) out.append(py::make_tuple(s.lw, s.m, s.nw));
