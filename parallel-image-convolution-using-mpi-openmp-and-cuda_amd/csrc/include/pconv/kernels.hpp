@@ -220,6 +220,18 @@ void clear_float_tuning();
 std::vector<std::pair<std::vector<int64_t>, SwarShape>> swar_tuned();
 // Tuned float entries: ({channels, uniform, steps, rows, row_bytes, batch, live}, shape); uniform 1: nine equal taps.
 std::vector<std::pair<std::vector<int64_t>, FloatShape>> float_tuned();
+// What ran (read-only, process-wide; tests assert that a forced kernel, shape
+// and form are what a launch took after tuned_choice's fallbacks): the most
+// recent launch issued to k_swar (kern 0) or k_swar_pf (kern 1), the tuner's
+// timed candidates included, and the most recent one issued to
+// k_float_temporal.  Before the first such launch: kern -1 / shape {0, 0}.
+struct SwarLaunchInfo {
+  int kern = -1;
+  SwarShape shape{0, 0, 0};
+  int form = -1;
+};
+SwarLaunchInfo last_swar_launch();
+FloatShape last_float_launch();
 
 // The 16-bit gaussian kernel's family (kernels/stencil_swar16.hip): lw is the
 // SAMPLES per lane (4 or 8: 8- or 16-byte lane loads), one column strip per

@@ -511,6 +511,9 @@ FloatShape pick_ft_shape(int steps, int ch, int64_t rows, int64_t row_bytes, int
   return most;  // a small frame: the shape with the most workgroups
 }
 
+// The most recent launch issued below, for last_float_launch(): m << 8 | nw.
+std::atomic<int> g_ft_last_launch{0};
+
 template <int CH, bool UNIFORM, int M, int NW>
 void launch_ft_shape(const StencilLaunch& a, const FloatTaps& tp, hipStream_t s) {
   const int images = a.images.images();
@@ -526,6 +529,7 @@ void launch_ft_shape(const StencilLaunch& a, const FloatTaps& tp, hipStream_t s)
       a.src, a.dst, a.pitch, static_cast<int>(a.row_bytes), static_cast<int>(a.r0), static_cast<int>(a.r1), a.steps,
       static_cast<int>(a.g_row0), static_cast<int>(std::min<int64_t>(a.height, int64_t(1) << 30)), tp,
       b.stride, b.dims, b.active, b.last_frame);
+  g_ft_last_launch.store(M << 8 | NW, std::memory_order_relaxed);
 }
 
 template <int CH, bool UNIFORM>
@@ -635,6 +639,11 @@ void prepare_float_temporal(const Filter& f, Channels ch, const StencilLaunch& a
 
 std::vector<FloatShape> float_shapes() {
   return std::vector<FloatShape>(std::begin(kFtShapes), std::end(kFtShapes));
+}
+
+FloatShape last_float_launch() {
+  const int v = g_ft_last_launch.load(std::memory_order_relaxed);
+  return FloatShape{v >> 8, v & 0xff};
 }
 
 void set_float_shape(int m, int nw) {

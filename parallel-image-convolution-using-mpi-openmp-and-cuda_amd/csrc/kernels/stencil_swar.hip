@@ -463,6 +463,10 @@ bool pf_launch_ok(const StencilLaunch& a, int steps) {
          (a.r1 - a.r0) * dp < (int64_t(1) << 31);
 }
 
+// The most recent launch issued below, for last_swar_launch(): one word,
+// valid << 31 | form << 25 | kern << 24 | lw << 16 | m << 8 | nw.
+std::atomic<uint32_t> g_last_launch{0};
+
 // One launch of row I of the table: the tile kernel, or (PF) the buffer-op one.
 template <int CH, size_t I, bool PF>
 void launch_tile(const StencilLaunch& a, hipStream_t s, int form) {
@@ -487,6 +491,10 @@ void launch_tile(const StencilLaunch& a, hipStream_t s, int form) {
     launch(swar_pf_kernel<CH, S.m, S.nw>(form, a.border), static_cast<int>(a.pitch));
   else
     launch(swar_kernel<CH, S.lw, S.m, S.nw>(form, a.border), a.pitch);
+  g_last_launch.store(0x80000000u | (form >= 1 ? 1u << 25 : 0u) | (PF ? 1u << 24 : 0u) |
+                          static_cast<uint32_t>(S.lw) << 16 | static_cast<uint32_t>(S.m) << 8 |
+                          static_cast<uint32_t>(S.nw),
+                      std::memory_order_relaxed);
 }
 
 // Shape override (tuning / tests): set_swar_shape().
@@ -512,6 +520,17 @@ void set_swar_shape(int lw, int m, int nw) {
   PCONV_CHECK(known_shape(s), "set_swar_shape: shape not instantiated");
   g_shape = s;
   g_have_shape = true;
+}
+
+SwarLaunchInfo last_swar_launch() {
+  const uint32_t v = g_last_launch.load(std::memory_order_relaxed);
+  SwarLaunchInfo r;
+  if (v >> 31) {
+    r.kern = static_cast<int>(v >> 24 & 1);
+    r.form = static_cast<int>(v >> 25 & 1);
+    r.shape = SwarShape{static_cast<int>(v >> 16 & 0xff), static_cast<int>(v >> 8 & 0xff), static_cast<int>(v & 0xff)};
+  }
+  return r;
 }
 
 std::vector<SwarShape> swar_shapes() {

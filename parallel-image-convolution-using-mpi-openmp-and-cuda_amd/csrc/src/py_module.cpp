@@ -611,6 +611,15 @@ PYBIND11_MODULE(_pconv_native, m) {
     for (const auto& s : swar_prefetch_shapes()) out.append(py::make_tuple(s.lw, s.m, s.nw));
     return out;
   });
+  m.def("last_swar_launch", []() {
+    const SwarLaunchInfo l = last_swar_launch();
+    return py::make_tuple(l.kern, l.shape.lw, l.shape.m, l.shape.nw, l.form);
+  }, "(kern, lw, m, nw, form) of the most recent launch issued to k_swar (kern 0) or k_swar_pf (kern 1); "
+     "kern -1 before the first.");
+  m.def("last_float_launch", []() {
+    const FloatShape s = last_float_launch();
+    return py::make_tuple(s.m, s.nw);
+  }, "(m, nw) of the most recent launch issued to k_float_temporal; (0, 0) before the first.");
   m.def("set_swar_alt", &set_swar_alt, py::arg("mode"),
         "SWAR step form: -1 tuned (default), 0 truncate every step, 1 pairs of steps with a x16 intermediate.");
   m.def("set_xcd_swizzle", &set_xcd_swizzle, py::arg("on"),

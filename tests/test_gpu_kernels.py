@@ -127,6 +127,17 @@ def _run_fused(native, img, steps, r0, r1, halo, g_row0, height, variant="auto",
     return gpu, cpu.reshape(h + 2 * halo, lay["pitch"])
 
 
+def _whole_frame(cpu, img, halo, r0, r1):
+    """The destination frame a launch on `img` must leave (_run_fused's frames
+    start as zeros): the reference's data columns in frame rows [r0, r1), zero
+    everywhere else — the pad columns and the rows between the written ones and
+    the canary included."""
+    rb = img.size // img.shape[0]
+    want = np.zeros_like(cpu)
+    want[halo + r0:halo + r1, 16:16 + rb] = cpu[halo + r0:halo + r1, 16:16 + rb]
+    return want
+
+
 @pytest.mark.parametrize("channels", ["grey", "rgb", "rgba"])
 @pytest.mark.parametrize("steps", [1, 2, 3, 4, 5, 8, 11, 16])
 def test_temporal_matches_fused_reference(native, rng, channels, steps, variant="temporal"):
@@ -198,6 +209,8 @@ def _band_regions(native, steps, variant, filt="gaussian"):
             assert np.array_equal(gpu[fr0:fr1], cpu[fr0:fr1]), (variant, g_row0, r0, r1, steps)
             # nothing written outside [r0, r1)
             assert (gpu[:fr0] == 0).all() and (gpu[fr1:] == 0).all()
+            # the whole destination frame: reference inside, zero outside
+            assert np.array_equal(gpu, _whole_frame(cpu, img, halo, r0, r1)), (variant, g_row0, r0, r1, steps)
 
 
 def test_temporal_equals_repeated_single_steps(pconv_mod, rng):
@@ -225,8 +238,10 @@ def test_every_swar_shape_bit_exact(native, rng, form):
                 img = rng.integers(0, 256, size=(71, 301, c) if c > 1 else (71, 301), dtype=np.uint8)
                 gpu, cpu = _run_fused(native, img, steps, 0, 71, steps, 0, 71, variant="temporal")
                 assert np.array_equal(gpu, cpu), (lw, m, nw, channels, steps)
+                assert np.array_equal(gpu, _whole_frame(cpu, img, steps, 0, img.shape[0])), "outside the image rows"
                 gpu, cpu = _run_fused(native, img[:40], steps, -5, 45, 16, 30, 200, variant="temporal")
-                assert np.array_equal(gpu[11:61], cpu[11:61]), (lw, m, nw, channels, steps, "band")
+                assert np.array_equal(gpu, _whole_frame(cpu, img[:40], 16, -5, 45)), \
+                    (lw, m, nw, channels, steps, "band")
     finally:
         native.set_swar_shape(0, 0, 0)
         native.set_swar_alt(-1)
@@ -253,8 +268,9 @@ def test_every_float_shape_bit_exact(native, rng, filt):
                     continue
                 gpu, cpu = _run_fused(native, img, steps, 0, 131, steps, 0, 131, variant="float_temporal", filt=f)
                 assert np.array_equal(gpu, cpu), (m, nw, img.shape, steps)
+                assert np.array_equal(gpu, _whole_frame(cpu, img, steps, 0, 131)), "outside the image rows"
                 gpu, cpu = _run_fused(native, img[:40], steps, -5, 45, 16, 30, 200, variant="float_temporal", filt=f)
-                assert np.array_equal(gpu[11:61], cpu[11:61]), (m, nw, img.shape, steps, "band")
+                assert np.array_equal(gpu, _whole_frame(cpu, img[:40], 16, -5, 45)), (m, nw, img.shape, steps, "band")
     finally:
         native.set_float_shape(0, 0)
 
@@ -280,8 +296,10 @@ def test_prefetch_kernel_every_shape_bit_exact(native, rng, form, swizzle):
                 img = rng.integers(0, 256, size=(131, w, c) if c > 1 else (131, w), dtype=np.uint8)
                 gpu, cpu = _run_fused(native, img, steps, 0, 131, steps, 0, 131, variant="temporal")
                 assert np.array_equal(gpu, cpu), (lw, m, nw, channels, steps)
+                assert np.array_equal(gpu, _whole_frame(cpu, img, steps, 0, img.shape[0])), "outside the image rows"
                 gpu, cpu = _run_fused(native, img[:40], steps, -5, 45, 16, 30, 200, variant="temporal")
-                assert np.array_equal(gpu[11:61], cpu[11:61]), (lw, m, nw, channels, steps, "band")
+                assert np.array_equal(gpu, _whole_frame(cpu, img[:40], 16, -5, 45)), \
+                    (lw, m, nw, channels, steps, "band")
     finally:
         native.set_prefetch_mode(-1)
         native.set_xcd_swizzle(True)
