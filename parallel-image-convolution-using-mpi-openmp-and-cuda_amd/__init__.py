@@ -31,7 +31,8 @@ from .ops.stencil import convolve, convolve_file, convolve_until_stable, residua
 from .ops.stencil import BatchEngine, convolve_batch, convolve_batch_until_stable, residual_batch  # noqa: E402
 from .ops.stencil import convolve_many, convolve_many_until_stable, residual_many, size_buckets  # noqa: E402
 from .models.pipeline import FilterPipeline  # noqa: E402
-from .ops.reference import numpy_convolve, numpy_residual  # noqa: E402
+from .ops.pyramid import Pyramid, pyramid  # noqa: E402
+from .ops.reference import numpy_convolve, numpy_decimate, numpy_residual  # noqa: E402
 from .utils.raw_io import read_raw, write_raw, output_path_for, synthetic_image  # noqa: E402
 
 __all__ = [
@@ -53,6 +54,9 @@ __all__ = [
     "size_buckets",
     "FilterPipeline",
     "numpy_convolve",
+    "numpy_decimate",
+    "Pyramid",
+    "pyramid",
     "residual",
     "convolve_until_stable",
     "numpy_residual",

@@ -68,6 +68,8 @@ struct ImageSize {
 // of the packed buffer that holds them back to back with tight rows.
 std::vector<ImageDims> image_dims_table(const ImageGeom& env, int capacity, const std::vector<ImageSize>& sizes);
 int64_t packed_bytes(const ImageGeom& env, const std::vector<ImageSize>& sizes);
+// Bytes of the same images decimated by `factor`, packed the same way.
+int64_t decimated_packed_bytes(const ImageGeom& env, const std::vector<ImageSize>& sizes, int factor);
 
 class BatchEngine {
  public:
@@ -104,6 +106,18 @@ class BatchEngine {
   // packing.  The next plain upload() ends the mode.
   void upload_sized(const uint8_t* p, const std::vector<ImageSize>& sizes, bool device = false);
   void download_sized(uint8_t* p, bool device = false);
+  // Decimated results (kernels.hpp launch_decimate, ONE launch for all images):
+  // every factor-th pixel of every factor-th row of the newest frames.
+  // download_decimated: n images of ceil(H / factor) x ceil(W / factor) pixels
+  // back to back with tight rows.  download_sized_decimated: image b of the
+  // current mixed-size upload as ceil(h_b / factor) rows of ceil(w_b / factor)
+  // pixels, at offset sum_{i<b} out_h_i x out_w_i x pixel bytes.  The kernel
+  // writes the caller's buffer where its layout allows (a uniform batch into
+  // device memory), otherwise staging frames of the decimated envelope
+  // (allocated on first use, never on a capturing stream) that one pitched
+  // copy per image empties.  Factor 1 is download / download_sized.
+  void download_decimated(uint8_t* p, int n, int factor, bool device = false);
+  void download_sized_decimated(uint8_t* p, int factor, bool device = false);
   // Sizes of the current mixed-size upload (empty: uniform launches).
   const std::vector<ImageSize>& sizes() const { return sizes_; }
   // Enqueue `reps` repetitions of images [0, n) (async).
@@ -151,6 +165,9 @@ class BatchEngine {
   void zero_words(uint8_t* p, size_t bytes);
   // One pitched copy per image between `packed` and the current frames.
   void copy_images(bool to_frames, uint8_t* packed, int n, const ImageDims* extents, bool device);
+  // The newest frames of images [0, n), decimated, into `packed`.
+  void decimate_images(uint8_t* packed, int n, int factor, const ImageDims* extents, bool device);
+  DeviceBuffer dec_stage_;  // staging frames of the decimated envelope (first use, regrown)
   // Rewrite `t` with n entries of entry_bytes each (`what` names it in errors).
   void stage(StagedTable& t, const char* what, const void* entries, size_t entry_bytes, size_t n);
   void upload_active(const std::vector<int32_t>& table);

@@ -48,6 +48,11 @@ struct CliConfig {
   // own (hip: one BatchEngine on 1 GPU; cpu / omp: a loop over the frames);
   // --synthetic makes frame k from seed + k.
   int frames = 1;
+  // --decimate S: the output holds every S-th pixel of every S-th row of each
+  // blurred frame (ceil(height / S) x ceil(width / S) pixels, phase 0); 1 = off.
+  // hip on 1 GPU (one decimation launch, a download of the kept bytes only) or
+  // the CPU backends (parse_cli names what it excludes).
+  int decimate = 1;
   bool check = false;
   bool json = false;
   int threads = 0;

@@ -67,6 +67,10 @@ class HostFrames {
   uint64_t residual() const;
   // The newest frame as contiguous rows.
   void copy_out(uint8_t* out) const;
+  // Every factor-th pixel of every factor-th row of the newest frame (phase 0)
+  // as contiguous rows: ceil(height / factor) rows of ceil(width / factor)
+  // whole pixels.  Factor 1 is copy_out.
+  void copy_out_decimated(uint8_t* out, int factor) const;
   // Chunks of `check_every` repetitions (the last one shorter), residual()
   // after each, at most max_reps repetitions; the final check is made even at
   // max_reps (repetitions 0: the input itself is checked).
@@ -84,8 +88,10 @@ class HostFrames {
 // reps steps on a contiguous image (pitch == row_bytes), zero-padded semantics
 // unless `border` says otherwise.
 // Ping-pongs internally; result written to `out` (may alias `in`).
+// decimate = s > 1: `out` receives out[Y][X] = result[Y * s][X * s] instead,
+// decimated_geom(geom, s).bytes() bytes (image.hpp).
 void cpu_convolve(const Filter& f, const ImageGeom& geom, const uint8_t* in, uint8_t* out,
-                  int reps, CpuBackend be, int threads = 0, Border border = Border::Zero);
+                  int reps, CpuBackend be, int threads = 0, Border border = Border::Zero, int decimate = 1);
 
 // Residual of the iterated map (the CPU twin of launch_residual): the number
 // of bytes in rows [r0, r1) of the frame that one more repetition would

@@ -183,6 +183,26 @@ class BandEngine {
                      hipStream_t stream = nullptr);
   void download_rows_device(uint8_t* dev, int64_t dev_pitch, int64_t r_begin, int64_t r_end);
 
+  // Decimated results (kernels.hpp launch_decimate): every factor-th pixel of
+  // the band's owned rows whose GLOBAL row is a multiple of `factor`, of the
+  // newest frame — decimated_rows(factor) rows of decimated_row_bytes(factor)
+  // bytes at `pitch`.  The device form's kernel writes straight to `dev`.  The
+  // host form's kernel writes a device staging buffer (allocated on first use,
+  // regrown when a call needs more, never on a capturing stream) and ONE
+  // pitched D2H of the decimated rows follows: the copy moves 1 / factor^2 of
+  // download_rows' bytes.  Factor 1 is download_rows / download_rows_device.
+  // Never part of process_graph or of a captured rep loop.
+  void download_rows_decimated(uint8_t* host, int64_t host_pitch, int factor, hipStream_t stream = nullptr);
+  void download_rows_decimated_device(uint8_t* dev, int64_t dev_pitch, int factor);
+  int64_t decimated_rows(int factor) const;
+  int64_t decimated_row_bytes(int factor) const;
+  // `src`'s newest frame, decimated, becomes this engine's current frame's
+  // rows (top-left at row 0 / column 0; this engine's geometry must be the
+  // decimated one, both engines whole images on one device): the kernel runs
+  // on this engine's compute stream behind an event on `src`'s.  A pyramid's
+  // next level never leaves the device.
+  void upload_decimated_from(const BandEngine& src, int factor);
+
   // Make the compute stream wait for work already queued on `s` / make `s`
   // wait for everything queued on the compute stream.
   void wait_stream(hipStream_t s);
@@ -286,6 +306,10 @@ class BandEngine {
   PinnedBuffer res_host_;             // pinned word the running count is read back into
   Event res_ev_;                      // the latest read-back has landed
   uint64_t res_seen_ = 0;             // the running count at the latest check read
+  DeviceBuffer dec_stage_;            // download_rows_decimated(): tight decimated rows (first use, regrown)
+  Event ev_dec_;                      // upload_decimated_from(): the source engine's frame is final
+  // launch_decimate of the newest frame's owned rows into dst (dst_bytes behind it) on s.
+  void launch_band_decimate(uint8_t* dst, int64_t dst_pitch, int64_t dst_bytes, int factor, hipStream_t s) const;
   Stream own_cs_, own_ms_;
   hipStream_t cs_ = nullptr, ms_ = nullptr;
   Event ev_ready_, ev_halo_, ev_t0_, ev_t1_, ev_sync_;

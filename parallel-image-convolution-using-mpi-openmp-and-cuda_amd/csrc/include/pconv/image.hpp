@@ -39,6 +39,22 @@ struct ImageGeom {
   void validate() const;
 };
 
+// Decimated results (factor s, phase 0): out[Y][X] = blurred[Y * s][X * s], an
+// image of ceil(H / s) x ceil(W / s) whole pixels.  The largest factor, the
+// extent ceil(n / s), and a geometry's decimated twin.
+constexpr int kMaxDecimate = 64;
+inline int64_t decimated_extent(int64_t n, int factor) { return (n + factor - 1) / factor; }
+inline void check_decimate(int factor) {
+  PCONV_CHECK(factor >= 1 && factor <= kMaxDecimate,
+              "decimate " + std::to_string(factor) + " is outside [1, " + std::to_string(kMaxDecimate) + "]");
+}
+inline ImageGeom decimated_geom(ImageGeom g, int factor) {
+  check_decimate(factor);
+  g.width = decimated_extent(g.width, factor);
+  g.height = decimated_extent(g.height, factor);
+  return g;
+}
+
 // Frame = rows [-halo, rows + halo) x bytes [-kPadLeft, pitch - kPadLeft).
 struct FrameLayout {
   int64_t row_bytes = 0;

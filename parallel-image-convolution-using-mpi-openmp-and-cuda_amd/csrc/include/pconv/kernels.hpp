@@ -153,6 +153,53 @@ void launch_residual(const Filter& f, Channels ch, const StencilLaunch& a, uint6
 // Rows one workgroup of the residual kernel covers (tests place image heights around it).
 constexpr int kResidualBlockRows = 32;
 
+// Decimation (kernels/decimate.hip): out[Y][X] = frame[first + Y * s][X * s],
+// whole pixels of `pixel_bytes` (channels x depth / 8: 1, 2, 3, 4, 6 or 8),
+// phase 0.  Frame row r is kept when (g_row0 + r) % s == 0, so the bands of an
+// image select by GLOBAL row; columns are never split.  The output of a frame
+// of `rows` x `row_bytes` has ceil((rows - first) / s) rows of
+// ceil(row_bytes / pixel_bytes / s) pixels and sits top-left in its
+// destination frame; no other destination byte is written, no source byte
+// outside [0, row_bytes) of the rows is read, and only selected source rows are
+// addressed at all.
+//   src / src_pitch / row_bytes / rows / g_row0: one pitched source frame, src
+// at (row 0, data column 0).  dst / dst_pitch: one pitched destination;
+// dst_bytes: the size of what dst points into, which the guards hold every
+// frame's output against.
+//   frames / src_stride / dst_stride: `frames` source frames src_stride bytes
+// apart go to destination frames dst_stride apart, all in one launch.
+//   dims / dims_host: optional table of `frames` SOURCE extents in the sense of
+// ImageSet::dims (the geometry above is then the envelope, g_row0 = 0); image
+// b's output extent is the ceil of its own extent, derived in the kernel.
+//   active / active_host: refused by name — a decimation covers every frame.
+// The source base, pitch and stride must be multiples of the load width (4 for
+// 4- and 8-byte pixels, 2 for 2 and 6); a destination whose base, pitch and
+// stride are multiples of 4 gets dword stores, any other byte stores.
+// Every guard is named "launch_decimate: ..."; a refused launch writes nothing.
+struct DecimateLaunch {
+  const uint8_t* src = nullptr;
+  int64_t src_pitch = 0;
+  int64_t row_bytes = 0;
+  int64_t rows = 0;
+  int64_t g_row0 = 0;
+  uint8_t* dst = nullptr;
+  int64_t dst_pitch = 0;
+  int64_t dst_bytes = 0;
+  int pixel_bytes = 1;
+  int factor = 1;
+  int frames = 1;
+  int64_t src_stride = 0;
+  int64_t dst_stride = 0;
+  const ImageDims* dims = nullptr;
+  const ImageDims* dims_host = nullptr;
+  const int32_t* active = nullptr;
+  const int32_t* active_host = nullptr;
+};
+void launch_decimate(const DecimateLaunch& a, hipStream_t stream);
+// Output rows one workgroup of k_decimate covers (tests place heights around
+// it); the factor's range and decimated_extent are image.hpp's.
+constexpr int kDecimateBlockRows = 16;
+
 // Whether `v` (or Auto) can fuse `steps` > 1 for this filter.
 bool supports_fusion(const Filter& f, KernelVariant v);
 

@@ -456,6 +456,16 @@ AppReport run_frames(const CliConfig& c) {
   if (!c.synthetic) validate_input_file(c.image, tall);
   const Filter f = Filter::by_name(c.filter);
   const int64_t rb = g.row_bytes(), fb = g.bytes();
+  // --decimate S: every frame's result is og (every S-th pixel of every S-th
+  // row), and the output file is `frames` of those back to back.  S = 1: og is
+  // g and every copy below is the plain one.
+  const int dec = c.decimate;
+  const ImageGeom og = decimated_geom(g, dec);
+  ImageGeom tall_out = og;
+  tall_out.height = og.height * c.frames;
+  const int64_t ofb = og.bytes();
+  std::vector<uint8_t> dec_out;  // cpu / omp, S > 1: the decimated frames (hip downloads them into `host`)
+  if (dec > 1 && c.backend != Backend::Hip) dec_out.resize(static_cast<size_t>(tall_out.bytes()));
   const auto load_frames = [&](uint8_t* dst) {
     if (!c.synthetic) return read_rows(c.image, tall, 0, tall.height, dst, rb);
     for (int k = 0; k < c.frames; ++k) synth_rows(g, c.seed + static_cast<uint64_t>(k), 0, g.height, dst + k * fb, rb);
@@ -505,8 +515,15 @@ AppReport run_frames(const CliConfig& c) {
     r.loop_s = wall_seconds() - l0;
     r.launches = eng.last_stats().launches;
     pc.mark("loop");
-    eng.download(host, c.frames);
-    eng.synchronize();
+    if (dec > 1) {
+      // One decimation launch for all frames, then the kept bytes only: the
+      // pinned input buffer (at least as large) receives them.
+      eng.download_decimated(host, c.frames, dec);
+      eng.synchronize();
+    } else {
+      eng.download(host, c.frames);
+      eng.synchronize();
+    }
     pc.mark("d2h");
     r.halo = static_cast<int>(eng.layout().halo);
     r.fuse = eng.options().fuse;
@@ -529,20 +546,25 @@ AppReport run_frames(const CliConfig& c) {
       const double l0 = wall_seconds();
       for (int done = 0; done < c.reps; ++done) fr.step();
       r.loop_s += wall_seconds() - l0;  // the repetitions alone, as for one image
-      fr.copy_out(host + k * fb);
+      if (dec > 1)
+        fr.copy_out_decimated(dec_out.data() + k * ofb, dec);
+      else
+        fr.copy_out(host + k * fb);
     }
   }
-  write_image(r.output, tall, host);
+  const uint8_t* result = dec_out.empty() ? host : dec_out.data();
+  write_image(r.output, tall_out, result);
   pc.mark("write");
   r.e2e_s = wall_seconds() - t0;
   if (c.check) {
     // every frame against the CPU oracle of that frame alone
-    std::vector<uint8_t> in(static_cast<size_t>(tall.bytes())), ref(static_cast<size_t>(fb));
+    // (decimated: the oracle's decimated copy-out of the same repetitions)
+    std::vector<uint8_t> in(static_cast<size_t>(tall.bytes())), ref(static_cast<size_t>(ofb));
     load_frames(in.data());
     r.mismatches = 0;
     for (int k = 0; k < c.frames; ++k) {
-      cpu_convolve(f, g, in.data() + k * fb, ref.data(), c.reps, CpuBackend::OpenMP, c.threads, c.border);
-      for (int64_t i = 0; i < fb; ++i) r.mismatches += ref[static_cast<size_t>(i)] != host[k * fb + i];
+      cpu_convolve(f, g, in.data() + k * fb, ref.data(), c.reps, CpuBackend::OpenMP, c.threads, c.border, dec);
+      for (int64_t i = 0; i < ofb; ++i) r.mismatches += ref[static_cast<size_t>(i)] != result[k * ofb + i];
     }
   }
   if (hip) r.since_exec_s = seconds_since_exec();
@@ -1237,8 +1259,11 @@ std::string run_bench(const CliConfig& c) { return run_bench_impl(c); }
 
 AppReport run_app(const CliConfig& c, JobCache* cache) {
   AppReport r;
-  if (c.frames > 1) {
-    PCONV_CHECK(cache == nullptr, "the resident service runs one image per job (--frames 1)");
+  if (c.frames > 1 || c.decimate > 1) {
+    // (--decimate above 1 takes the frames path for one frame too: its hip
+    // branch downloads through the batch engine's one decimation launch)
+    PCONV_CHECK(cache == nullptr, c.frames > 1 ? "the resident service runs one image per job (--frames 1)"
+                                               : "the resident service runs no decimated job (--decimate 1)");
     r = run_frames(c);
     r.gpus = c.backend == Backend::Hip ? 1 : 0;
   } else if (c.backend == Backend::Auto && cache == nullptr && c.checkpoint_every == 0 && c.converge_every == 0) {
@@ -1289,6 +1314,9 @@ std::string report_json(const CliConfig& c, const AppReport& r) {
     os << ", \"reps_done\": " << r.reps_done << ", \"converged\": " << (r.converged ? "true" : "false")
        << ", \"residual\": " << r.residual;
   if (!r.copies.empty()) os << ", \"copies\": \"" << r.copies << "\"";
+  if (c.decimate > 1)  // (the rates above still count input pixels)
+    os << ", \"decimate\": " << c.decimate << ", \"out_width\": " << decimated_extent(c.width, c.decimate)
+       << ", \"out_height\": " << decimated_extent(c.height, c.decimate);
   if (!r.phases.empty()) {
     os << ", \"phases_s\": {";
     for (size_t i = 0; i < r.phases.size(); ++i)

@@ -163,6 +163,87 @@ void BatchEngine::download_sized(uint8_t* p, bool device) {
   copy_images(false, p, static_cast<int>(dims_host_.size()), dims_host_.data(), device);
 }
 
+// ---- decimated results --------------------------------------------------------
+// ONE launch_decimate for all n images.  A uniform batch into device memory
+// goes straight to the caller's buffer (tight rows, frames back to back: the
+// kernel's byte stores take any alignment).  Everything else — host memory, and
+// mixed sizes, whose packed images have a row pitch each — goes through staging
+// frames of the decimated envelope, from which one pitched copy per image (the
+// copies of copy_images) moves the image regions.
+
+void BatchEngine::decimate_images(uint8_t* p, int n, int factor, const ImageDims* extents, bool device) {
+  check_decimate(factor);
+  if (n == 0) return;
+  PCONV_CHECK(!stream_capturing(cs_), "BatchEngine: a decimated download is not captured into a hipGraph");
+  const int64_t pb = geom_.pixel_bytes();
+  const ImageGeom og = decimated_geom(geom_, factor);
+  const int64_t orb = og.row_bytes(), oh = og.height;
+  DecimateLaunch d;
+  d.src = frame_at(cur_);
+  d.src_pitch = lay_.pitch;
+  d.row_bytes = lay_.row_bytes;
+  d.rows = lay_.rows;
+  d.pixel_bytes = static_cast<int>(pb);
+  d.factor = factor;
+  d.frames = n;
+  d.src_stride = stride_;
+  if (extents) {
+    d.dims = reinterpret_cast<const ImageDims*>(dims_.dev.data());
+    d.dims_host = extents;
+  }
+  if (device && !extents) {
+    d.dst = p;
+    d.dst_pitch = orb;
+    d.dst_stride = oh * orb;
+    d.dst_bytes = n * oh * orb;
+    launch_decimate(d, cs_);
+    return;
+  }
+  const int64_t sp = round_up<int64_t>(orb, 16), sstride = oh * sp;
+  const size_t need = static_cast<size_t>(sstride * capacity_);
+  if (dec_stage_.size() < need) {
+    PCONV_HIP_CHECK(hipStreamSynchronize(cs_));  // no earlier copy still reads the buffer that goes
+    dec_stage_ = DeviceBuffer(need);
+  }
+  d.dst = dec_stage_.data();
+  d.dst_pitch = sp;
+  d.dst_stride = sstride;
+  d.dst_bytes = static_cast<int64_t>(dec_stage_.size());
+  launch_decimate(d, cs_);
+  const hipMemcpyKind kind = device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  for (int b = 0; b < n; ++b) {
+    const int64_t rb = extents ? decimated_extent(extents[b].row_bytes / pb, factor) * pb : orb;
+    const int64_t rows = extents ? decimated_extent(extents[b].height, factor) : oh;
+    const uint8_t* src = dec_stage_.data() + b * sstride;
+    if (opt_.kernel_copies)
+      launch_copy_rows(src, sp, p, rb, rb, rows, cs_);
+    else
+      PCONV_HIP_CHECK(hipMemcpy2DAsync(p, rb, src, sp, rb, rows, kind, cs_));
+    p += rb * rows;
+  }
+}
+
+void BatchEngine::download_decimated(uint8_t* p, int n, int factor, bool device) {
+  check_n("BatchEngine::download_decimated", n);
+  PCONV_CHECK(sizes_.empty(), "BatchEngine::download_decimated: the upload was mixed-size (download_sized_decimated)");
+  PCONV_CHECK(p != nullptr || n == 0, "BatchEngine::download_decimated: null destination");
+  if (factor == 1) return download(p, n, device);
+  decimate_images(p, n, factor, nullptr, device);
+}
+
+void BatchEngine::download_sized_decimated(uint8_t* p, int factor, bool device) {
+  PCONV_CHECK(p != nullptr || sizes_.empty(), "BatchEngine::download_sized_decimated: null destination");
+  if (factor == 1) return download_sized(p, device);
+  decimate_images(p, static_cast<int>(dims_host_.size()), factor, dims_host_.data(), device);
+}
+
+int64_t decimated_packed_bytes(const ImageGeom& env, const std::vector<ImageSize>& sizes, int factor) {
+  int64_t total = 0;
+  for (const auto& z : sizes)
+    total += decimated_extent(z.width, factor) * decimated_extent(z.height, factor) * env.pixel_bytes();
+  return total;
+}
+
 // What every launch over images [0, n) of the current frames shares: whole
 // images, the extents table in mixed mode, the table of open images while a
 // compacting run_until_stable has retired some.

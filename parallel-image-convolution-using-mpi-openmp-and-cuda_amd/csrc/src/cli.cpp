@@ -57,6 +57,13 @@ std::string help_text(const std::string& prog) {
          "                            frames advance in the same fused launches on 1 GPU; --synthetic makes\n"
          "                            frame k from SEED + k.  Not with --gpus > 1, --server, --bench,\n"
          "                            --backend auto, --checkpoint-every, --converge-every, --graph\n"
+         "  --decimate S              keep every S-th pixel of every S-th row of the result (1..64, default 1):\n"
+         "                            the output holds ceil(height / S) x ceil(width / S) pixels per frame, pixel\n"
+         "                            (0, 0) always kept; hip: one decimation launch, only the kept bytes are\n"
+         "                            downloaded.  --backend hip (1 GPU) | cpu | omp, with --border, --filter,\n"
+         "                            --fuse, --frames, --depth 16, --synthetic, --out, --kernel.  Not with\n"
+         "                            --gpus > 1, --server, --bench, --backend auto, --converge-every,\n"
+         "                            --checkpoint-every, --graph\n"
          "  --check                   verify the result against the CPU oracle\n"
          "  --json                    print a JSON metrics line\n"
          "  --threads N               OpenMP threads for --backend omp\n"
@@ -163,6 +170,8 @@ CliConfig parse_cli(const std::vector<std::string>& args) {
       c.depth = v == "16" ? 16 : 8;
     } else if (a == "--frames") {
       c.frames = static_cast<int>(parse_int(next("--frames"), "--frames", 1, 1 << 20));
+    } else if (a == "--decimate") {
+      c.decimate = static_cast<int>(parse_int(next("--decimate"), "--decimate", 1, kMaxDecimate));
     } else if (a == "--check") {
       c.check = true;
     } else if (a == "--json") {
@@ -273,6 +282,18 @@ CliConfig parse_cli(const std::vector<std::string>& args) {
     if (c.graph) refuse("--graph");
     if (c.variant != KernelVariant::Auto && c.variant != KernelVariant::Temporal)
       refuse("--kernel other than auto|temporal");
+  }
+  if (c.decimate > 1) {
+    const auto refuse = [](const std::string& what) {
+      PCONV_FAIL("--decimate above 1 cannot be combined with " + what);
+    };
+    if (c.gpus > 1) refuse("--gpus above 1");
+    if (!c.server.empty()) refuse("--server");
+    if (c.bench_steps > 0) refuse("--bench");
+    if (c.backend == Backend::Auto) refuse("--backend auto");
+    if (c.converge_every > 0) refuse("--converge-every");
+    if (c.checkpoint_every > 0) refuse("--checkpoint-every");
+    if (c.graph) refuse("--graph (the decimated download is not captured into a hipGraph)");
   }
   if (c.emulate_world > 0 && (c.bench_steps == 0 || c.gpus != 1))
     PCONV_FAIL("--emulate needs --bench and --gpus 1 (one process times one rank of the split)");

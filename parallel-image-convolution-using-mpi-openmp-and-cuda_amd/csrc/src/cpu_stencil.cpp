@@ -452,6 +452,19 @@ void HostFrames::copy_out(uint8_t* out) const {
     std::memcpy(out + r * rb, cur_.data() + lay_.offset(r), static_cast<size_t>(rb));
 }
 
+void HostFrames::copy_out_decimated(uint8_t* out, int factor) const {
+  if (factor == 1) return copy_out(out);
+  const ImageGeom og = decimated_geom(geom_, factor);
+  const int64_t pb = geom_.pixel_bytes(), orb = og.row_bytes(), hop = pb * factor;
+  const bool omp = be_ == CpuBackend::OpenMP;
+#pragma omp parallel for schedule(static) if (omp)
+  for (int64_t y = 0; y < og.height; ++y) {
+    const uint8_t* s = cur_.data() + lay_.offset(y * factor);
+    uint8_t* d = out + y * orb;
+    for (int64_t x = 0; x < og.width; ++x) std::memcpy(d + x * pb, s + x * hop, static_cast<size_t>(pb));
+  }
+}
+
 StableStats HostFrames::run_until_stable(int max_reps, int check_every) {
   PCONV_CHECK(max_reps >= 0, "repetitions must be >= 0");
   PCONV_CHECK(check_every >= 1, "check_every must be >= 1");
@@ -468,13 +481,14 @@ StableStats HostFrames::run_until_stable(int max_reps, int check_every) {
 }
 
 void cpu_convolve(const Filter& f, const ImageGeom& geom, const uint8_t* in, uint8_t* out, int reps, CpuBackend be,
-                  int threads, Border border) {
+                  int threads, Border border, int decimate) {
   HostFrames fr(f, geom, be, border);
   PCONV_CHECK(reps >= 0, "repetitions must be >= 0");
+  check_decimate(decimate);
   fr.load(in);
   TeamScope team(be, threads);
   for (int t = 0; t < reps; ++t) fr.step();
-  fr.copy_out(out);
+  fr.copy_out_decimated(out, decimate);
 }
 
 uint64_t cpu_image_residual(const Filter& f, const ImageGeom& geom, const uint8_t* in, CpuBackend be, int threads,

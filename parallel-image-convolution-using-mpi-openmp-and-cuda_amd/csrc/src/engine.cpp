@@ -158,6 +158,93 @@ void BandEngine::download_rows_device(uint8_t* dev, int64_t dev_pitch, int64_t r
                                    r_end - r_begin, hipMemcpyDeviceToDevice, cs_));
 }
 
+// ---- decimated results ------------------------------------------------------
+
+int64_t BandEngine::decimated_rows(int factor) const {
+  check_decimate(factor);
+  const int64_t first = (factor - band_.y0 % factor) % factor;  // first owned row on a kept global row
+  return lay_.rows > first ? decimated_extent(lay_.rows - first, factor) : 0;
+}
+
+int64_t BandEngine::decimated_row_bytes(int factor) const {
+  check_decimate(factor);
+  return decimated_extent(geom_.width, factor) * geom_.pixel_bytes();
+}
+
+void BandEngine::launch_band_decimate(uint8_t* dst, int64_t dst_pitch, int64_t dst_bytes, int factor,
+                                      hipStream_t s) const {
+  DecimateLaunch d;
+  d.src = src_frame();
+  d.src_pitch = lay_.pitch;
+  d.row_bytes = lay_.row_bytes;
+  d.rows = lay_.rows;
+  d.g_row0 = band_.y0;
+  d.dst = dst;
+  d.dst_pitch = dst_pitch;
+  d.dst_bytes = dst_bytes;
+  d.pixel_bytes = geom_.pixel_bytes();
+  d.factor = factor;
+  launch_decimate(d, s);
+}
+
+void BandEngine::download_rows_decimated_device(uint8_t* dev, int64_t dev_pitch, int factor) {
+  const int64_t oh = decimated_rows(factor), orb = decimated_row_bytes(factor);
+  if (factor == 1) return download_rows_device(dev, dev_pitch, 0, lay_.rows);
+  PCONV_CHECK(dev_pitch >= orb, "download_rows_decimated_device: pitch < decimated row bytes");
+  if (oh == 0) return;
+  PCONV_CHECK(!stream_capturing(cs_), "download_rows_decimated_device: not captured into a hipGraph");
+  launch_band_decimate(dev, dev_pitch, (oh - 1) * dev_pitch + orb, factor, cs_);
+}
+
+void BandEngine::download_rows_decimated(uint8_t* host, int64_t host_pitch, int factor, hipStream_t stream) {
+  const int64_t oh = decimated_rows(factor), orb = decimated_row_bytes(factor);
+  if (factor == 1) return download_rows(host, host_pitch, 0, lay_.rows, stream);
+  PCONV_CHECK(host_pitch >= orb, "download_rows_decimated: host pitch < decimated row bytes");
+  if (oh == 0) return;
+  hipStream_t s = stream ? stream : cs_;
+  PCONV_CHECK(!stream_capturing(s) && !stream_capturing(cs_),
+              "download_rows_decimated: not captured into a hipGraph (the staging buffer and the kernel stay "
+              "outside process_graph)");
+  // Staging rows at a 16-byte multiple: dword stores, and the row copy's vectors.
+  const int64_t sp = round_up<int64_t>(orb, 16);
+  const size_t need = static_cast<size_t>(oh * sp);
+  if (dec_stage_.size() < need) {
+    PCONV_HIP_CHECK(hipStreamSynchronize(s));  // no earlier copy still reads the buffer that goes
+    if (s != cs_) PCONV_HIP_CHECK(hipStreamSynchronize(cs_));
+    dec_stage_ = DeviceBuffer(need);
+  }
+  launch_band_decimate(dec_stage_.data(), sp, static_cast<int64_t>(dec_stage_.size()), factor, s);
+  if (opt_.kernel_copies)
+    launch_copy_rows(dec_stage_.data(), sp, host, host_pitch, orb, oh, s);
+  else
+    PCONV_HIP_CHECK(hipMemcpy2DAsync(host, host_pitch, dec_stage_.data(), sp, orb, oh, hipMemcpyDeviceToHost, s));
+}
+
+void BandEngine::upload_decimated_from(const BandEngine& src, int factor) {
+  check_decimate(factor);
+  PCONV_CHECK(&src != this, "upload_decimated_from: an engine cannot be its own source");
+  PCONV_CHECK(src.opt_.device == opt_.device, "upload_decimated_from: both engines must be on one device");
+  PCONV_CHECK(src.band_.y0 == 0 && src.band_.rows == src.geom_.height && band_.y0 == 0 &&
+                  band_.rows == geom_.height,
+              "upload_decimated_from: whole images only (no row bands)");
+  const ImageGeom og = decimated_geom(src.geom_, factor);
+  PCONV_CHECK(og.width == geom_.width && og.height == geom_.height && src.geom_.channels == geom_.channels &&
+                  src.geom_.depth == geom_.depth,
+              "upload_decimated_from: this engine's geometry is not the source's decimated by " +
+                  std::to_string(factor));
+  PCONV_CHECK(!stream_capturing(cs_) && !stream_capturing(src.cs_),
+              "upload_decimated_from: not captured into a hipGraph");
+  if (!ev_dec_.get()) ev_dec_ = Event::create();
+  if (src.cs_ != cs_) {
+    ev_dec_.record(src.cs_);
+    ev_dec_.wait_on(cs_);
+  }
+  // The frame's pads and ghost rows keep their zeros: the kernel writes
+  // [0, row_bytes) of rows [0, rows) only (dst_bytes ends with the last row).
+  src.launch_band_decimate(src_frame(), lay_.pitch, (lay_.rows - 1) * lay_.pitch + lay_.row_bytes, factor, cs_);
+  halo_valid_ = false;
+}
+
 void BandEngine::read_frame_rows(uint8_t* host, int64_t r_begin, int64_t r_end) {
   PCONV_CHECK(r_begin >= -lay_.halo && r_end <= lay_.rows + lay_.halo && r_begin <= r_end,
               "read_frame_rows: rows outside frame");

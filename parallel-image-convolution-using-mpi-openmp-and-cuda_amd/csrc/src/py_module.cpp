@@ -191,18 +191,20 @@ PYBIND11_MODULE(_pconv_native, m) {
   m.def(
       "cpu_convolve",
       [](py::buffer in, py::buffer out, int64_t w, int64_t h, const std::string& ch, int reps, py::object filter,
-         bool omp, int threads, const std::string& border, int depth) {
+         bool omp, int threads, const std::string& border, int depth, int decimate) {
         const ImageGeom g = make_geom(w, h, ch, depth);
         const Border bd = parse_border(border);
         const HostView a = host_view(in, false), b = host_view(out, true);
-        PCONV_CHECK(a.size == g.bytes() && b.size == g.bytes(), "buffer size does not match the image geometry");
+        PCONV_CHECK(a.size == g.bytes() && b.size == decimated_geom(g, decimate).bytes(),
+                    "buffer size does not match the image geometry");
         const Filter f = make_filter(filter);
         py::gil_scoped_release nogil;
-        cpu_convolve(f, g, a.ptr, b.ptr, reps, omp ? CpuBackend::OpenMP : CpuBackend::Serial, threads, bd);
+        cpu_convolve(f, g, a.ptr, b.ptr, reps, omp ? CpuBackend::OpenMP : CpuBackend::Serial, threads, bd, decimate);
       },
       py::arg("src"), py::arg("dst"), py::arg("width"), py::arg("height"), py::arg("channels"), py::arg("reps"),
       py::arg("filter") = "gaussian", py::arg("omp") = false, py::arg("threads") = 0, py::arg("border") = "zero",
-      py::arg("depth") = 8);
+      py::arg("depth") = 8, py::arg("decimate") = 1);
+  m.attr("MAX_DECIMATE") = kMaxDecimate;
   m.def("default_cpu_threads", &default_cpu_threads,
         "OpenMP team size used when none is set: affinity CPUs capped by the cgroup quota, minus one");
   m.def(
@@ -549,6 +551,67 @@ PYBIND11_MODULE(_pconv_native, m) {
       "with an active table, on the `batch` frames it names out of `batch_frames`, each adding to its frame's "
       "counter; synchronises the stream.");
   m.attr("RESIDUAL_BLOCK_ROWS") = kResidualBlockRows;
+  m.def(
+      "launch_decimate",
+      [](uintptr_t src, int64_t src_pitch, int64_t row_bytes, int64_t rows, uintptr_t dst, int64_t dst_pitch,
+         int64_t dst_bytes, int pixel_bytes, int factor, int64_t g_row0, int frames, int64_t src_stride,
+         int64_t dst_stride, uintptr_t stream, py::object dims, uintptr_t dims_ptr, py::object active,
+         uintptr_t active_ptr, int timed) {
+        DecimateLaunch a;
+        a.src = reinterpret_cast<const uint8_t*>(src);
+        a.src_pitch = src_pitch;
+        a.row_bytes = row_bytes;
+        a.rows = rows;
+        a.g_row0 = g_row0;
+        a.dst = reinterpret_cast<uint8_t*>(dst);
+        a.dst_pitch = dst_pitch;
+        a.dst_bytes = dst_bytes;
+        a.pixel_bytes = pixel_bytes;
+        a.factor = factor;
+        a.frames = frames;
+        a.src_stride = src_stride;
+        a.dst_stride = dst_stride;
+        std::vector<ImageDims> dims_host;
+        if (!dims.is_none()) {
+          for (const auto& d : dims.cast<std::vector<std::pair<int32_t, int32_t>>>())
+            dims_host.push_back(ImageDims{d.first, d.second});
+          PCONV_CHECK(static_cast<int64_t>(dims_host.size()) == frames,
+                      "dims: the list must hold `frames` (row_bytes, height) pairs");
+          a.dims_host = dims_host.data();
+        }
+        a.dims = reinterpret_cast<const ImageDims*>(dims_ptr);
+        std::vector<int32_t> active_host;
+        if (!active.is_none()) {
+          active_host = active.cast<std::vector<int32_t>>();
+          a.active_host = active_host.data();
+        }
+        a.active = reinterpret_cast<const int32_t*>(active_ptr);
+        hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+        std::vector<double> ms;
+        py::gil_scoped_release nogil;
+        launch_decimate(a, s);
+        // diagnostics: `timed` more launches, each between two timing events on the stream
+        std::vector<Event> ev;
+        for (int i = 0; i < 2 * timed; ++i) ev.push_back(Event::create(true));
+        for (int i = 0; i < timed; ++i) {
+          ev[2 * i].record(s);
+          launch_decimate(a, s);
+          ev[2 * i + 1].record(s);
+        }
+        PCONV_HIP_CHECK(hipStreamSynchronize(s));
+        for (int i = 0; i < timed; ++i) ms.push_back(Event::elapsed_ms(ev[2 * i], ev[2 * i + 1]));
+        return ms;
+      },
+      py::arg("src"), py::arg("src_pitch"), py::arg("row_bytes"), py::arg("rows"), py::arg("dst"),
+      py::arg("dst_pitch"), py::arg("dst_bytes"), py::arg("pixel_bytes"), py::arg("factor"), py::arg("g_row0") = 0,
+      py::arg("frames") = 1, py::arg("src_stride") = 0, py::arg("dst_stride") = 0, py::arg("stream") = 0,
+      py::arg("dims") = py::none(), py::arg("dims_ptr") = 0, py::arg("active") = py::none(),
+      py::arg("active_ptr") = 0, py::arg("timed") = 0,
+      "Decimation kernel on raw pointers: every factor-th pixel of the source frame's rows on a kept global row "
+      "into the pitched destination (dst_bytes: the size of what dst points into); `frames` frames at the two "
+      "strides in one launch, dims / dims_ptr: their SOURCE extents; an active table is refused; synchronises the "
+      "stream.  timed = k: k further launches of the same arguments, returns the ms of each (stream events).");
+  m.attr("DECIMATE_BLOCK_ROWS") = kDecimateBlockRows;
   m.def("set_swar_shape", &set_swar_shape, py::arg("lw") = 0, py::arg("m") = 0, py::arg("nw") = 0,
         "Force the SWAR temporal tile shape (lw=0: back to the latency model).");
   m.def("swar_shapes", []() {
@@ -750,6 +813,29 @@ PYBIND11_MODULE(_pconv_native, m) {
               e.download_rows(reinterpret_cast<uint8_t*>(ptr), pitch, r_begin, r_end);
           },
           py::arg("ptr"), py::arg("pitch"), py::arg("r_begin"), py::arg("r_end"), py::arg("device") = false)
+      .def(
+          "download_decimated",
+          [](BandEngine& e, py::buffer host, int factor) {
+            const HostView v = host_view(host, true);
+            PCONV_CHECK(v.size >= e.decimated_rows(factor) * e.decimated_row_bytes(factor), "host buffer too small");
+            e.download_rows_decimated(v.ptr, e.decimated_row_bytes(factor), factor);
+          },
+          py::arg("host"), py::arg("factor"),
+          "every factor-th pixel of the owned rows on a kept global row of the newest frame, tight rows: one "
+          "decimation launch into device staging and one D2H of the decimated bytes")
+      .def(
+          "download_decimated_ptr",
+          [](BandEngine& e, uintptr_t ptr, int64_t pitch, int factor, bool device) {
+            if (device)
+              e.download_rows_decimated_device(reinterpret_cast<uint8_t*>(ptr), pitch, factor);
+            else
+              e.download_rows_decimated(reinterpret_cast<uint8_t*>(ptr), pitch, factor);
+          },
+          py::arg("ptr"), py::arg("pitch"), py::arg("factor"), py::arg("device") = false)
+      .def("decimated_rows", &BandEngine::decimated_rows, py::arg("factor"))
+      .def("decimated_row_bytes", &BandEngine::decimated_row_bytes, py::arg("factor"))
+      .def("upload_decimated_from", &BandEngine::upload_decimated_from, py::arg("src"), py::arg("factor"),
+           "src's newest frame, decimated, becomes this engine's current frame (device to device, one launch)")
       .def("set_halo_valid", &BandEngine::set_halo_valid)
       .def("wait_stream", [](BandEngine& e, uintptr_t s) { e.wait_stream(reinterpret_cast<hipStream_t>(s)); })
       .def("signal_stream", [](BandEngine& e, uintptr_t s) { e.signal_stream(reinterpret_cast<hipStream_t>(s)); })
@@ -939,6 +1025,37 @@ PYBIND11_MODULE(_pconv_native, m) {
           "download_sized_ptr",
           [](BatchEngine& e, uintptr_t ptr, bool device) { e.download_sized(reinterpret_cast<uint8_t*>(ptr), device); },
           py::arg("ptr"), py::arg("device") = false)
+      .def(
+          "download_decimated",
+          [](BatchEngine& e, py::buffer host, int n, int factor) {
+            const HostView v = host_view(host, true);
+            PCONV_CHECK(n >= 0 && v.size >= n * decimated_geom(e.geom(), factor).bytes(), "host buffer too small");
+            e.download_decimated(v.ptr, n, factor);
+          },
+          py::arg("host"), py::arg("n"), py::arg("factor"),
+          "images [0, n) decimated by `factor` in ONE launch, packed back to back with tight rows")
+      .def(
+          "download_decimated_ptr",
+          [](BatchEngine& e, uintptr_t ptr, int n, int factor, bool device) {
+            e.download_decimated(reinterpret_cast<uint8_t*>(ptr), n, factor, device);
+          },
+          py::arg("ptr"), py::arg("n"), py::arg("factor"), py::arg("device") = false)
+      .def(
+          "download_sized_decimated",
+          [](BatchEngine& e, py::buffer host, int factor) {
+            const HostView v = host_view(host, true);
+            check_decimate(factor);
+            PCONV_CHECK(v.size >= decimated_packed_bytes(e.geom(), e.sizes(), factor), "host buffer too small");
+            e.download_sized_decimated(v.ptr, factor);
+          },
+          py::arg("host"), py::arg("factor"),
+          "the current mixed-size upload's images, each decimated by `factor` (ONE launch), packed back to back")
+      .def(
+          "download_sized_decimated_ptr",
+          [](BatchEngine& e, uintptr_t ptr, int factor, bool device) {
+            e.download_sized_decimated(reinterpret_cast<uint8_t*>(ptr), factor, device);
+          },
+          py::arg("ptr"), py::arg("factor"), py::arg("device") = false)
       .def_property_readonly("sizes",
                              [](const BatchEngine& e) {
                                std::vector<std::pair<int64_t, int64_t>> out;

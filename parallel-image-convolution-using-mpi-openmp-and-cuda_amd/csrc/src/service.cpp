@@ -153,6 +153,7 @@ int serve_main(const ServeOptions& o) {
         CliConfig c = parse_cli(args);
         PCONV_CHECK(c.server.empty(), "service: a job cannot name another server");
         PCONV_CHECK(c.depth == 8, "service: --depth 16 cannot run as a served job");
+        PCONV_CHECK(c.decimate == 1, "service: --decimate above 1 cannot run as a served job");
         PCONV_CHECK(o.device >= 0 || c.backend != Backend::Hip, "service: this server has no GPU (--device -1)");
         const AppReport r = run_app(c, cache.get());
         reply = report_json(c, r);

@@ -50,25 +50,32 @@ class FilterPipeline:
     def __repr__(self) -> str:
         return "FilterPipeline(" + ",".join(f"{s.filter.name}:{s.reps}" for s in self.stages) + ")"
 
-    def apply(self, image, backend: str = "auto", device: Optional[int] = None, border: str = "zero"):
+    def apply(self, image, backend: str = "auto", device: Optional[int] = None, border: str = "zero",
+              decimate: int = 1):
         """Run every stage in order (each under the same ``border`` rule); returns
-        the same container type as ``image``."""
-        from ..ops.reference import refuse_depth16
+        the same container type as ``image``.  ``decimate`` applies after the
+        last stage (``convolve``'s keyword)."""
+        from ..ops.reference import check_decimate, refuse_depth16
         from ..ops.stencil import convolve
 
         refuse_depth16(image, "FilterPipeline")
+        factor = check_decimate(decimate)
         out = image
-        for s in self.stages:
-            if s.reps:
-                out = convolve(out, s.reps, s.filter, backend=backend, device=device, border=border)
+        stages = [s for s in self.stages if s.reps]
+        for i, s in enumerate(stages):
+            last = factor if i == len(stages) - 1 else 1
+            out = convolve(out, s.reps, s.filter, backend=backend, device=device, border=border, decimate=last)
+        if not stages and factor > 1:  # nothing to run: the slicing alone, through the same entry point
+            out = convolve(out, 0, "gaussian", backend=backend, device=device, border=border, decimate=factor)
         return out
 
-    def reference(self, image, border: str = "zero"):
+    def reference(self, image, border: str = "zero", decimate: int = 1):
         """Independent NumPy oracle of the whole pipeline."""
-        from ..ops.reference import numpy_convolve, refuse_depth16
+        from ..ops.reference import check_decimate, numpy_convolve, numpy_decimate, refuse_depth16
 
         refuse_depth16(image, "FilterPipeline")
+        factor = check_decimate(decimate)
         out = image
         for s in self.stages:
             out = numpy_convolve(out, s.reps, s.filter, border)
-        return out
+        return numpy_decimate(out, factor) if factor > 1 else out

@@ -96,6 +96,32 @@ def numpy_convolve(img: np.ndarray, reps: int = 1, filt="gaussian", border: str 
     return out
 
 
+MAX_DECIMATE = 64
+
+
+def check_decimate(decimate) -> int:
+    """A decimation factor: an integer in [1, 64] (``ValueError`` otherwise)."""
+    if isinstance(decimate, bool) or not isinstance(decimate, (int, np.integer)):
+        raise ValueError(f"decimate must be an integer in [1, {MAX_DECIMATE}], got {decimate!r}")
+    if not 1 <= int(decimate) <= MAX_DECIMATE:
+        raise ValueError(f"decimate must be an integer in [1, {MAX_DECIMATE}], got {decimate!r}")
+    return int(decimate)
+
+
+def decimated_shape(shape, s: int) -> tuple:
+    """Shape of an ``(H, W[, C])`` image decimated by ``s``: ceil of H and W."""
+    return (-(-int(shape[0]) // s), -(-int(shape[1]) // s)) + tuple(int(d) for d in shape[2:])
+
+
+def numpy_decimate(img: np.ndarray, s: int) -> np.ndarray:
+    """Every ``s``-th pixel of every ``s``-th row, phase 0 (pixel (0, 0) is
+    always kept): ``img[::s, ::s]`` as a contiguous array of
+    ``ceil(H / s) x ceil(W / s)`` pixels.  ``decimate=s`` of every entry point
+    returns ``numpy_decimate(<the undecimated result>, s)``."""
+    s = check_decimate(s)
+    return np.ascontiguousarray(np.asarray(img)[::s, ::s])
+
+
 def numpy_residual(img: np.ndarray, filt="gaussian", border: str = "zero") -> int:
     """Bytes of ``img`` that one more repetition would change; 0 means ``img``
     is a fixed point of the iterated map.  By definition

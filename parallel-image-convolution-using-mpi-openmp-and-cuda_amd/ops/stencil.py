@@ -25,7 +25,8 @@ import torch
 
 from .._native import require_native
 from ..models.filters import get_filter
-from .reference import check_border, check_depth16_filter, numpy_convolve, numpy_residual, numpy_step
+from .reference import (check_border, check_decimate, check_depth16_filter, decimated_shape, numpy_convolve,
+                        numpy_decimate, numpy_residual, numpy_step)
 
 _CHANNELS = {1: "grey", 3: "rgb", 4: "rgba"}
 _CH_COUNT = {"grey": 1, "rgb": 3, "rgba": 4}
@@ -164,35 +165,47 @@ class Engine:
         if image_depth(img) != self.depth and (self.depth == 8 or isinstance(img, torch.Tensor)):
             raise TypeError(f"engine of depth {self.depth} got a {img.dtype} image")
 
-    def run_numpy(self, img: np.ndarray, reps: int) -> np.ndarray:
+    def run_numpy(self, img: np.ndarray, reps: int, decimate: int = 1) -> np.ndarray:
+        """``decimate=s``: every s-th pixel of every s-th row of the result
+        (``numpy_decimate``) — one decimation launch on the device, and only the
+        kept bytes are downloaded."""
+        s = check_decimate(decimate)
         self._check_samples(img)
         src = _host_samples(img, self.depth)
-        out = np.empty_like(src)
+        out = np.empty_like(src) if s == 1 else np.empty(decimated_shape(src.shape, s), dtype=src.dtype)
         self._eng.upload(_bytes_of(src), 0, self.height)
         self._eng.run(int(reps))
-        self._eng.download(_bytes_of(out), 0, self.height)
+        if s == 1:
+            self._eng.download(_bytes_of(out), 0, self.height)
+        else:
+            self._eng.download_decimated(_bytes_of(out), s)
         self._eng.synchronize()
         return out
 
-    def run_tensor(self, t: torch.Tensor, reps: int) -> torch.Tensor:
+    def run_tensor(self, t: torch.Tensor, reps: int, decimate: int = 1) -> torch.Tensor:
+        s = check_decimate(decimate)
         self._check_samples(t)
         if t.device.type != "cuda":
-            return torch.from_numpy(self.run_numpy(t.numpy(), reps))
+            return torch.from_numpy(self.run_numpy(t.numpy(), reps, s))
         src = t.contiguous()
-        out = torch.empty_like(src)
+        out = (torch.empty_like(src) if s == 1 else
+               torch.empty(decimated_shape(src.shape, s), dtype=src.dtype, device=src.device))
         ts = torch.cuda.current_stream(src.device).cuda_stream
         self._eng.wait_stream(ts)
         self._eng.upload_ptr(src.data_ptr(), self.row_bytes, 0, self.height, device=True)
         self._eng.run(int(reps))
-        self._eng.download_ptr(out.data_ptr(), self.row_bytes, 0, self.height, device=True)
+        if s == 1:
+            self._eng.download_ptr(out.data_ptr(), self.row_bytes, 0, self.height, device=True)
+        else:  # the kernel writes the result tensor itself
+            self._eng.download_decimated_ptr(out.data_ptr(), self._eng.decimated_row_bytes(s), s, device=True)
         self._eng.signal_stream(ts)
         src.record_stream(torch.cuda.current_stream(src.device))
         return out
 
-    def __call__(self, img, reps: int):
+    def __call__(self, img, reps: int, decimate: int = 1):
         if isinstance(img, torch.Tensor):
-            return self.run_tensor(img, reps)
-        return self.run_numpy(np.asarray(img), reps)
+            return self.run_tensor(img, reps, decimate)
+        return self.run_numpy(np.asarray(img), reps, decimate)
 
     # ---- fixed point -------------------------------------------------
     def _with_frame(self, img, work):
@@ -269,7 +282,7 @@ def _default_backend() -> str:
 
 def convolve(image, reps: int = 1, filter="gaussian", backend: str = "auto", device: Optional[int] = None,
              fuse: Optional[int] = None, graph: bool = False, variant: str = "auto", threads: int = 0,
-             border: str = "zero"):
+             border: str = "zero", decimate: int = 1):
     """Apply ``reps`` 3x3 convolutions to an 8-bit image, or (dtype ``uint16``,
     NumPy or ``torch.uint16``: depth 16, the gaussian only) to a 16-bit one.
 
@@ -277,11 +290,19 @@ def convolve(image, reps: int = 1, filter="gaussian", backend: str = "auto", dev
     reference's zero padding) or ``"replicate"`` (the nearest image pixel: no
     dark frame after many repetitions), on every backend.
 
+    ``decimate=s`` (an integer in 1..64): return every s-th pixel of every s-th
+    row of the result, ``out[Y, X] = blurred[Y * s, X * s]`` with
+    ``ceil(H / s) x ceil(W / s)`` pixels (pixel (0, 0) is always kept) —
+    ``numpy_decimate(convolve(image, reps, ...), s)`` on every backend.  On
+    ``hip`` the slicing is one kernel launch and only the kept bytes are
+    copied back; ``s = 1`` is the plain call, launch for launch.
+
     Returns the same container type as the input (NumPy array or torch tensor
     on the same device).
     """
     if reps < 0:
         raise ValueError("reps must be >= 0")
+    s = check_decimate(decimate)
     flt = get_filter(filter)
     check_border(border)
     is_tensor = isinstance(image, torch.Tensor)
@@ -297,21 +318,28 @@ def convolve(image, reps: int = 1, filter="gaussian", backend: str = "auto", dev
     if backend == "numpy":
         arr = image.cpu().numpy() if is_tensor else np.asarray(image)
         out = numpy_convolve(arr, reps, flt, border)
+        if s > 1:
+            out = numpy_decimate(out, s)
         return torch.from_numpy(out).to(image.device) if is_tensor else out
 
     if backend in ("cpu", "omp"):
         n = require_native()
         arr = _host_samples(image, depth)
-        out = np.empty_like(arr)
-        n.cpu_convolve(_bytes_of(arr), _bytes_of(out), w, h, ch, int(reps), flt.to_native(), backend == "omp",
-                       int(threads), border=border, depth=depth)
+        if s == 1:
+            out = np.empty_like(arr)
+            n.cpu_convolve(_bytes_of(arr), _bytes_of(out), w, h, ch, int(reps), flt.to_native(), backend == "omp",
+                           int(threads), border=border, depth=depth)
+        else:
+            out = np.empty(decimated_shape(arr.shape, s), dtype=arr.dtype)
+            n.cpu_convolve(_bytes_of(arr), _bytes_of(out), w, h, ch, int(reps), flt.to_native(), backend == "omp",
+                           int(threads), border=border, depth=depth, decimate=s)
         return torch.from_numpy(out).to(image.device) if is_tensor else out
 
     if backend == "hip":
         if device is None:
             device = image.device.index if (is_tensor and image.is_cuda) else 0
         eng = _cached_engine(w, h, ch, flt, int(device or 0), fuse, graph, variant, border, depth)
-        return eng(image, reps)
+        return eng(image, reps) if s == 1 else eng(image, reps, s)
 
     raise ValueError(f"unknown backend {backend!r} (hip|omp|cpu|numpy|auto)")
 
@@ -453,18 +481,28 @@ class BatchEngine:
             raise ValueError(f"{shape[0]} images exceed the engine's capacity {self.capacity}")
         return shape[0]
 
-    def _transfer(self, flat, n: int, work, sizes=None):
+    def _transfer(self, flat, n: int, work, sizes=None, decimate: int = 1):
         """The bracket every call shares.  ``flat``: the packed samples of ``n``
         images, a 1-D NumPy array or CUDA tensor (which never leaves the
         device); ``sizes``: their ``[(width, height)]``, or ``None`` for images
         of the engine's geometry.  Waits for the caller's stream, uploads,
         ``work(n)`` on the resident frames, downloads the newest frames in the
         same packing, signals the caller's stream (host memory: synchronises):
-        ``(out, work's result)``, ``(out, None)`` for no images."""
+        ``(out, work's result)``, ``(out, None)`` for no images.  ``decimate``
+        above 1: the download is the decimated one (one launch for all images)
+        and ``out`` holds the decimated images in the same packing."""
         e = self._eng
         self._n = n
+        s = decimate
         device = isinstance(flat, torch.Tensor)
-        out = torch.empty_like(flat) if device else np.empty_like(flat)
+        if s == 1:
+            out = torch.empty_like(flat) if device else np.empty_like(flat)
+        else:
+            c = _CH_COUNT[self.channels]
+            dims = sizes if sizes is not None else [(self.width, self.height)] * n
+            count = sum(-(-w // s) * -(-h // s) * c for w, h in dims)
+            out = (torch.empty(count, dtype=flat.dtype, device=flat.device) if device
+                   else np.empty(count, dtype=flat.dtype))
         if n == 0:
             return out, None
         form = ("" if sizes is None else "_sized") + ("_ptr" if device else "")
@@ -474,8 +512,10 @@ class BatchEngine:
             e.wait_stream(ts)
         getattr(e, "upload" + form)(flat.data_ptr() if device else _bytes_of(flat), n if sizes is None else sizes, **kw)
         res = work(n)
-        getattr(e, "download" + form)(out.data_ptr() if device else _bytes_of(out), *([n] if sizes is None else []),
-                                      **kw)
+        name = ("download" + form) if s == 1 else (
+            "download" + ("" if sizes is None else "_sized") + "_decimated" + ("_ptr" if device else ""))
+        getattr(e, name)(out.data_ptr() if device else _bytes_of(out), *([n] if sizes is None else []),
+                         *([] if s == 1 else [s]), **kw)
         if device:
             e.signal_stream(ts)
             flat.record_stream(torch.cuda.current_stream(flat.device))
@@ -483,15 +523,15 @@ class BatchEngine:
             e.synchronize()
         return out, res
 
-    def _with_frames(self, stack, work):
+    def _with_frames(self, stack, work, decimate: int = 1):
         """:meth:`_transfer` of a stack: ``(out stack in the input's container,
         work's result)``."""
         is_tensor = isinstance(stack, torch.Tensor)
         on_gpu = is_tensor and stack.device.type == "cuda"
         self._check_samples(stack)
         src = stack.contiguous() if on_gpu else _host_samples(stack, self.depth)
-        out, res = self._transfer(src.reshape(-1), self._check_stack(src.shape), work)
-        out = out.reshape(src.shape)
+        out, res = self._transfer(src.reshape(-1), self._check_stack(src.shape), work, None, decimate)
+        out = out.reshape((int(src.shape[0]),) + decimated_shape(src.shape[1:], decimate))
         return (torch.from_numpy(out) if is_tensor and not on_gpu else out), res
 
     _check_samples = Engine._check_samples
@@ -500,16 +540,20 @@ class BatchEngine:
         if self.depth == 16:
             raise ValueError(f"{what}: depth 16 not supported")
 
-    def run_numpy(self, stack: np.ndarray, reps: int) -> np.ndarray:
-        return self._with_frames(np.asarray(stack), lambda n: self._eng.run(int(reps), n))[0]
+    def run_numpy(self, stack: np.ndarray, reps: int, decimate: int = 1) -> np.ndarray:
+        """``decimate=s``: every image comes back as ``numpy_decimate(result,
+        s)`` — ONE decimation launch for the whole stack."""
+        s = check_decimate(decimate)
+        return self._with_frames(np.asarray(stack), lambda n: self._eng.run(int(reps), n), s)[0]
 
-    def run_tensor(self, stack: torch.Tensor, reps: int) -> torch.Tensor:
-        return self._with_frames(stack, lambda n: self._eng.run(int(reps), n))[0]
+    def run_tensor(self, stack: torch.Tensor, reps: int, decimate: int = 1) -> torch.Tensor:
+        s = check_decimate(decimate)
+        return self._with_frames(stack, lambda n: self._eng.run(int(reps), n), s)[0]
 
-    def __call__(self, stack, reps: int):
+    def __call__(self, stack, reps: int, decimate: int = 1):
         if isinstance(stack, torch.Tensor):
-            return self.run_tensor(stack, reps)
-        return self.run_numpy(stack, reps)
+            return self.run_tensor(stack, reps, decimate)
+        return self.run_numpy(stack, reps, decimate)
 
     # ---- fixed points ------------------------------------------------
     def _residual(self, images, bracket) -> np.ndarray:
@@ -563,7 +607,7 @@ class BatchEngine:
             sizes.append((w, h))
         return seq, sizes
 
-    def _with_images(self, images, work):
+    def _with_images(self, images, work, decimate: int = 1):
         """:meth:`_transfer` of a sequence of images of any sizes within the
         envelope, each top-left in its frame: ``([out], work's result)``, every
         output in its input's container."""
@@ -577,22 +621,25 @@ class BatchEngine:
         else:
             flat = np.concatenate([_host_samples(im, self.depth).reshape(-1) for im in seq]
                                   or [np.empty(0, _NP_DTYPE[self.depth])])
-        out, res = self._transfer(flat, len(seq), work, sizes)
+        out, res = self._transfer(flat, len(seq), work, sizes, decimate)
         outs, at = [], 0
         for im, t in zip(seq, tensors):
-            k = int(np.prod(tuple(im.shape)))
-            piece = out[at:at + k].reshape(tuple(im.shape))
+            shape = decimated_shape(tuple(im.shape), decimate)
+            k = int(np.prod(shape))
+            piece = out[at:at + k].reshape(shape)
             at += k
             if not on_gpu:
                 piece = torch.from_numpy(piece.copy()) if t else piece.copy()
             outs.append(piece)
         return outs, res
 
-    def run_images(self, images, reps: int) -> list:
+    def run_images(self, images, reps: int, decimate: int = 1) -> list:
         """``reps`` repetitions of every image of the sequence, each as a lone
         image of its own size; a list in input order, in the input's container
-        type (CUDA tensors stay on the device)."""
-        return self._with_images(images, lambda n: self._eng.run(int(reps), n))[0]
+        type (CUDA tensors stay on the device).  ``decimate=s``: entry b is
+        ``numpy_decimate`` of image b's result, all from one launch."""
+        s = check_decimate(decimate)
+        return self._with_images(images, lambda n: self._eng.run(int(reps), n), s)[0]
 
     def residual_images(self, images=None) -> np.ndarray:
         """:meth:`residual` for mixed sizes: of ``images``, or (``None``) of the
@@ -711,7 +758,7 @@ def _hip_batch_engine(stack, is_tensor, geo, flt, device, fuse, variant, border,
 
 def convolve_batch(images, reps: int = 1, filter="gaussian", backend: str = "auto", device: Optional[int] = None,
                    fuse: Optional[int] = None, variant: str = "auto", threads: int = 0, border: str = "zero",
-                   batch_size: Optional[int] = None):
+                   batch_size: Optional[int] = None, decimate: int = 1):
     """``convolve`` for N same-size 8-bit images at once.
 
     ``images``: an ``(N, H, W)`` array or tensor (grey), an ``(N, H, W, C)``
@@ -724,24 +771,29 @@ def convolve_batch(images, reps: int = 1, filter="gaussian", backend: str = "aut
     :class:`BatchEngine`, ``batch_size`` at a time (the last chunk shorter).
     ``batch_size=None``: the largest n <= N whose two device allocations stay
     within 1 GiB (at least 1) — a memory policy, not a tuned number.  The
-    other backends loop over the images.
+    other backends loop over the images.  ``decimate=s``: every image of the
+    result is decimated as by :func:`convolve` (``hip``: one decimation launch
+    per chunk).
     """
     if reps < 0:
         raise ValueError("reps must be >= 0")
+    s = check_decimate(decimate)
     flt, stack, is_tensor, geo, backend = _prepare_batch(images, filter, backend, border, batch_size)
     _check_depth(image_depth(stack), flt, variant if backend == "hip" else "auto")
     n_img = int(stack.shape[0])
     if n_img == 0:
-        return _empty_like_stack(stack, is_tensor)
+        empty = _empty_like_stack(stack, is_tensor)
+        return empty if s == 1 else empty[:, ::s, ::s]
 
     if backend != "hip":
-        outs = [convolve(stack[i], reps, flt, backend=backend, threads=threads, border=border) for i in range(n_img)]
+        outs = [convolve(stack[i], reps, flt, backend=backend, threads=threads, border=border, decimate=s)
+                for i in range(n_img)]
         return torch.stack(outs) if is_tensor else np.stack(outs)
 
     eng, cap = _hip_batch_engine(stack, is_tensor, geo, flt, device, fuse, variant, border, batch_size)
     if n_img <= cap:
-        return eng(stack, reps)
-    outs = [eng(stack[i:i + cap], reps) for i in range(0, n_img, cap)]
+        return eng(stack, reps, s)
+    outs = [eng(stack[i:i + cap], reps, s) for i in range(0, n_img, cap)]
     return torch.cat(outs) if is_tensor else np.concatenate(outs)
 
 
@@ -916,7 +968,7 @@ def _hip_buckets(seq, is_tensor, ch, flt, device, fuse, variant, border, batch_s
 
 def convolve_many(images, reps: int = 1, filter="gaussian", backend: str = "auto", device: Optional[int] = None,
                   fuse: Optional[int] = None, variant: str = "auto", threads: int = 0, border: str = "zero",
-                  batch_size: Optional[int] = None, min_fill: float = 0.5) -> list:
+                  batch_size: Optional[int] = None, min_fill: float = 0.5, decimate: int = 1) -> list:
     """``convolve`` for a sequence of 8-bit images of ANY sizes.
 
     ``images``: uint8 ``(H, W)`` / ``(H, W, C)`` arrays or tensors that share
@@ -929,18 +981,21 @@ def convolve_many(images, reps: int = 1, filter="gaussian", backend: str = "auto
     in the fused launches of one cached :class:`BatchEngine` whose geometry is
     the bucket's envelope: ``ceil(reps / fuse)`` launches per bucket whatever
     its images' number and sizes.  The other backends loop over the images.
+    ``decimate=s``: entry i is decimated as by :func:`convolve` (``hip``: one
+    decimation launch per bucket).
     """
     if reps < 0:
         raise ValueError("reps must be >= 0")
+    s = check_decimate(decimate)
     flt, seq, is_tensor, ch, backend = _prepare_many(images, filter, backend, border, batch_size, min_fill)
     if not seq:
         return []
     _check_depth(image_depth(seq[0]), flt, variant if backend == "hip" else "auto")
     if backend != "hip":
-        return [convolve(im, reps, flt, backend=backend, threads=threads, border=border) for im in seq]
+        return [convolve(im, reps, flt, backend=backend, threads=threads, border=border, decimate=s) for im in seq]
     outs = [None] * len(seq)
     for eng, idx in _hip_buckets(seq, is_tensor, ch, flt, device, fuse, variant, border, batch_size, min_fill):
-        for i, o in zip(idx, eng.run_images([seq[i] for i in idx], reps)):
+        for i, o in zip(idx, eng.run_images([seq[i] for i in idx], reps, s)):
             outs[i] = o
     return outs
 
@@ -994,14 +1049,15 @@ def residual_many(images, filter="gaussian", backend: str = "auto", device: Opti
 
 def convolve_file(path: str, width: int, height: int, reps: int, channels: str = "grey", filter="gaussian",
                   out: Optional[str] = None, backend: str = "auto", device: Optional[int] = None,
-                  border: str = "zero", depth: int = 8) -> str:
+                  border: str = "zero", depth: int = 8, decimate: int = 1) -> str:
     """The reference program in one call (``cuda/main.c:10-53``): read the raw
     image, ``reps`` repetitions, write ``blur_<name>`` (or ``out``); returns the
-    output path."""
+    output path.  ``decimate=s``: the file holds the decimated result,
+    ``ceil(height / s) x ceil(width / s)`` pixels."""
     from ..utils.raw_io import output_path_for, read_raw, write_raw
 
     img = read_raw(path, width, height, channels, depth=depth)
-    res = convolve(img, reps, filter, backend=backend, device=device, border=border)
+    res = convolve(img, reps, filter, backend=backend, device=device, border=border, decimate=decimate)
     dst = out or output_path_for(path)
     write_raw(dst, res)
     return dst
