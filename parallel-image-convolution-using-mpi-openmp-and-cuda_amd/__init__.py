@@ -32,7 +32,8 @@ from .ops.stencil import BatchEngine, convolve_batch, convolve_batch_until_stabl
 from .ops.stencil import convolve_many, convolve_many_until_stable, residual_many, size_buckets  # noqa: E402
 from .models.pipeline import FilterPipeline  # noqa: E402
 from .ops.pyramid import Pyramid, pyramid  # noqa: E402
-from .ops.reference import numpy_convolve, numpy_decimate, numpy_residual  # noqa: E402
+from .ops.stencil import unsharp, unsharp_batch, unsharp_many  # noqa: E402
+from .ops.reference import numpy_convolve, numpy_decimate, numpy_residual, numpy_unsharp  # noqa: E402
 from .utils.raw_io import read_raw, write_raw, output_path_for, synthetic_image  # noqa: E402
 
 __all__ = [
@@ -57,6 +58,10 @@ __all__ = [
     "numpy_decimate",
     "Pyramid",
     "pyramid",
+    "unsharp",
+    "unsharp_batch",
+    "unsharp_many",
+    "numpy_unsharp",
     "residual",
     "convolve_until_stable",
     "numpy_residual",

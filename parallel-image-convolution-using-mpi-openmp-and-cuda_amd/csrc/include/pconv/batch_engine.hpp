@@ -118,6 +118,16 @@ class BatchEngine {
   // copy per image empties.  Factor 1 is download / download_sized.
   void download_decimated(uint8_t* p, int n, int factor, bool device = false);
   void download_sized_decimated(uint8_t* p, int factor, bool device = false);
+  // Unsharp mask (kernels.hpp launch_unsharp) of images [0, n), ONE launch each:
+  // snapshot_original(n) copies the current frames' rows into a third
+  // allocation (first use, never on a capturing stream) after the upload and
+  // before run(); apply_unsharp(k, threshold, n) then combines the newest
+  // frames with them in place, image by image — a uniform batch through
+  // `frames` and the stride, a mixed-size upload through its extents table —
+  // so download / download_sized return the sharpened images.  Both refuse by
+  // name while an active-image table is in force.
+  void snapshot_original(int n);
+  void apply_unsharp(int k, int threshold, int n);
   // Sizes of the current mixed-size upload (empty: uniform launches).
   const std::vector<ImageSize>& sizes() const { return sizes_; }
   // Enqueue `reps` repetitions of images [0, n) (async).
@@ -168,6 +178,8 @@ class BatchEngine {
   // The newest frames of images [0, n), decimated, into `packed`.
   void decimate_images(uint8_t* packed, int n, int factor, const ImageDims* extents, bool device);
   DeviceBuffer dec_stage_;  // staging frames of the decimated envelope (first use, regrown)
+  DeviceBuffer orig_;       // snapshot_original(): `capacity` frames laid out like frame_ (first use)
+  int orig_n_ = 0;          // images the snapshot holds (0: none, or already consumed)
   // Rewrite `t` with n entries of entry_bytes each (`what` names it in errors).
   void stage(StagedTable& t, const char* what, const void* entries, size_t entry_bytes, size_t n);
   void upload_active(const std::vector<int32_t>& table);

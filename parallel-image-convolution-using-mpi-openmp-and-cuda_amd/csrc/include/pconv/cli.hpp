@@ -53,6 +53,13 @@ struct CliConfig {
   // hip on 1 GPU (one decimation launch, a download of the kept bytes only) or
   // the CPU backends (parse_cli names what it excludes).
   int decimate = 1;
+  // --unsharp A: the output is x + A (x - blur(x)) per sample (unsharp mask);
+  // unsharp_k = A x 16, an integer in [1, 255], 0 = off.  --unsharp-threshold T:
+  // samples with |x - blur(x)| < T keep x.  hip on 1 GPU (the original stays on
+  // the device) or the CPU backends (parse_cli names what it excludes).
+  int unsharp_k = 0;
+  int64_t unsharp_threshold = 0;
+  bool unsharp_threshold_set = false;
   bool check = false;
   bool json = false;
   int threads = 0;

@@ -93,6 +93,26 @@ class HostFrames {
 void cpu_convolve(const Filter& f, const ImageGeom& geom, const uint8_t* in, uint8_t* out,
                   int reps, CpuBackend be, int threads = 0, Border border = Border::Zero, int decimate = 1);
 
+// Unsharp mask (the CPU twin of launch_unsharp, kernels.hpp): per sample of
+// three tight images of `geom` (pitch == row_bytes, depth 16: host byte order),
+// with x from `orig`, b from `blurred`, d = x - b and max = 255 | 65535,
+//   out = x                                           if |d| < threshold
+//   out = clamp((x (16 + k) - b k + 8) >> 4, 0, max)  otherwise
+// in 32-bit integers (arithmetic shift).  `out` may be `blurred` or `orig`
+// (a sample is read before it is written).
+void cpu_unsharp(const ImageGeom& geom, const uint8_t* orig, const uint8_t* blurred, uint8_t* out, int k,
+                 int threshold, CpuBackend be, int threads = 0);
+// cpu_convolve followed by cpu_unsharp against the input: x + (k / 16)(x -
+// blur(x)).  `out` may alias `in`.
+void cpu_unsharp_convolve(const Filter& f, const ImageGeom& geom, const uint8_t* in, uint8_t* out, int reps, int k,
+                          int threshold, CpuBackend be, int threads = 0, Border border = Border::Zero);
+// The argument checks every backend shares.  unsharp_k: amount x 16 as an exact
+// integer in [1, 255], else "unsharp amount must be a multiple of 1/16 in
+// [0.0625, 15.9375], got ...".  check_unsharp: k in [1, 255] and threshold in
+// [0, max of the depth], else an error of the same shape.
+int unsharp_k(double amount);
+void check_unsharp(int k, int64_t threshold, int depth);
+
 // Residual of the iterated map (the CPU twin of launch_residual): the number
 // of bytes in rows [r0, r1) of the frame that one more repetition would
 // change.  cpu_step's row kernels into a scratch row, compared and counted —

@@ -203,6 +203,17 @@ class BandEngine {
   // next level never leaves the device.
   void upload_decimated_from(const BandEngine& src, int factor);
 
+  // Unsharp mask (kernels.hpp launch_unsharp): x + (k / 16)(x - blur(x)).
+  // snapshot_original() copies the owned rows of the current frame into a third
+  // device buffer of the frames' pitch (allocated on first use, never on a
+  // capturing stream; launch_copy_rows on the compute stream): call it after
+  // the upload, before run().  apply_unsharp() then combines the newest frame
+  // with that original, in place, so every download path returns the sharpened
+  // rows unchanged.  The image is uploaded once and the original never again.
+  // Neither call is ever part of process_graph or of a captured rep loop.
+  void snapshot_original();
+  void apply_unsharp(int k, int threshold);
+
   // Make the compute stream wait for work already queued on `s` / make `s`
   // wait for everything queued on the compute stream.
   void wait_stream(hipStream_t s);
@@ -308,6 +319,8 @@ class BandEngine {
   uint64_t res_seen_ = 0;             // the running count at the latest check read
   DeviceBuffer dec_stage_;            // download_rows_decimated(): tight decimated rows (first use, regrown)
   Event ev_dec_;                      // upload_decimated_from(): the source engine's frame is final
+  DeviceBuffer orig_;                 // snapshot_original(): the owned rows at lay_.pitch (first use)
+  bool orig_valid_ = false;           // orig_ holds a snapshot no upload has followed
   // launch_decimate of the newest frame's owned rows into dst (dst_bytes behind it) on s.
   void launch_band_decimate(uint8_t* dst, int64_t dst_pitch, int64_t dst_bytes, int factor, hipStream_t s) const;
   Stream own_cs_, own_ms_;

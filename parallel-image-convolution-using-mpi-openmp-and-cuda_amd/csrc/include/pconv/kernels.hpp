@@ -200,6 +200,54 @@ void launch_decimate(const DecimateLaunch& a, hipStream_t stream);
 // it); the factor's range and decimated_extent are image.hpp's.
 constexpr int kDecimateBlockRows = 16;
 
+// Unsharp mask (kernels/unsharp.hip): per sample, with x from `orig`, b from
+// `blur`, d = x - b and max = 255 (depth 8) or 65535 (depth 16, host byte order),
+//   dst = x                                           if |d| < threshold
+//   dst = clamp((x (16 + k) - b k + 8) >> 4, 0, max)  otherwise
+// (arithmetic shift, 32-bit integers): x + (k / 16)(x - b), rounded to nearest.
+// Only [0, row_bytes) of rows [0, rows) of a destination frame is written; the
+// row's last lane LOADS up to round_up(row_bytes, 16) of both sources, which
+// the guards keep inside every pitch.
+//   orig / orig_pitch, blur / blur_pitch, dst / dst_pitch: three pitched frames
+// of `rows` x `row_bytes`, each pointer at (row 0, data column 0).  dst == blur
+// with equal pitch and stride is in place (a lane reads its bytes before it
+// writes them); any other overlap of dst with orig or blur is refused.
+//   depth: 8 | 16 (row_bytes a whole number of samples).  k: amount x 16, in
+// [1, 255].  threshold: in [0, max].
+//   frames / orig_stride / blur_stride / dst_stride: `frames` frames at those
+// strides (each >= a frame), all in one launch.
+//   dims / dims_host: optional table of `frames` extents in the sense of
+// ImageSet::dims (the geometry above is then the envelope; image b occupies
+// rows [0, height_b) and bytes [0, row_bytes_b) of its frames).
+//   active / active_host: refused by name — every frame is sharpened.
+// Every base, pitch and stride must be a multiple of 16 and every pitch
+// >= round_up(row_bytes, 16).
+// Every guard is named "launch_unsharp: ..."; a refused launch writes nothing.
+struct UnsharpLaunch {
+  const uint8_t* orig = nullptr;
+  int64_t orig_pitch = 0;
+  const uint8_t* blur = nullptr;
+  int64_t blur_pitch = 0;
+  uint8_t* dst = nullptr;
+  int64_t dst_pitch = 0;
+  int64_t row_bytes = 0;
+  int64_t rows = 0;
+  int depth = 8;
+  int k = 16;
+  int threshold = 0;
+  int frames = 1;
+  int64_t orig_stride = 0;
+  int64_t blur_stride = 0;
+  int64_t dst_stride = 0;
+  const ImageDims* dims = nullptr;
+  const ImageDims* dims_host = nullptr;
+  const int32_t* active = nullptr;
+  const int32_t* active_host = nullptr;
+};
+void launch_unsharp(const UnsharpLaunch& a, hipStream_t stream);
+// Rows one workgroup of k_unsharp covers (tests place heights around it).
+constexpr int kUnsharpBlockRows = 16;
+
 // Whether `v` (or Auto) can fuse `steps` > 1 for this filter.
 bool supports_fusion(const Filter& f, KernelVariant v);
 

@@ -507,6 +507,8 @@ AppReport run_frames(const CliConfig& c) {
       pc.mark("warmup");
     }
     eng.upload(host, c.frames);
+    // --unsharp: the originals stay on the device (one copy launch for all frames)
+    if (c.unsharp_k > 0) eng.snapshot_original(c.frames);
     eng.synchronize();
     pc.mark("h2d");
     const double l0 = wall_seconds();
@@ -515,6 +517,12 @@ AppReport run_frames(const CliConfig& c) {
     r.loop_s = wall_seconds() - l0;
     r.launches = eng.last_stats().launches;
     pc.mark("loop");
+    if (c.unsharp_k > 0) {
+      // one pointwise launch, in place on the newest frames: the plain download follows
+      eng.apply_unsharp(c.unsharp_k, static_cast<int>(c.unsharp_threshold), c.frames);
+      eng.synchronize();
+      pc.mark("unsharp");
+    }
     if (dec > 1) {
       // One decimation launch for all frames, then the kept bytes only: the
       // pinned input buffer (at least as large) receives them.
@@ -546,10 +554,17 @@ AppReport run_frames(const CliConfig& c) {
       const double l0 = wall_seconds();
       for (int done = 0; done < c.reps; ++done) fr.step();
       r.loop_s += wall_seconds() - l0;  // the repetitions alone, as for one image
-      if (dec > 1)
+      if (c.unsharp_k > 0) {
+        // the frame's original still sits in `host`: blurred copy beside it, combined in place
+        std::vector<uint8_t> blurred(static_cast<size_t>(fb));
+        fr.copy_out(blurred.data());
+        cpu_unsharp(g, host + k * fb, blurred.data(), host + k * fb, c.unsharp_k, static_cast<int>(c.unsharp_threshold),
+                    be, c.threads);
+      } else if (dec > 1) {
         fr.copy_out_decimated(dec_out.data() + k * ofb, dec);
-      else
+      } else {
         fr.copy_out(host + k * fb);
+      }
     }
   }
   const uint8_t* result = dec_out.empty() ? host : dec_out.data();
@@ -563,7 +578,11 @@ AppReport run_frames(const CliConfig& c) {
     load_frames(in.data());
     r.mismatches = 0;
     for (int k = 0; k < c.frames; ++k) {
-      cpu_convolve(f, g, in.data() + k * fb, ref.data(), c.reps, CpuBackend::OpenMP, c.threads, c.border, dec);
+      if (c.unsharp_k > 0)  // (never with --decimate above 1: ofb is fb)
+        cpu_unsharp_convolve(f, g, in.data() + k * fb, ref.data(), c.reps, c.unsharp_k,
+                             static_cast<int>(c.unsharp_threshold), CpuBackend::OpenMP, c.threads, c.border);
+      else
+        cpu_convolve(f, g, in.data() + k * fb, ref.data(), c.reps, CpuBackend::OpenMP, c.threads, c.border, dec);
       for (int64_t i = 0; i < ofb; ++i) r.mismatches += ref[static_cast<size_t>(i)] != result[k * ofb + i];
     }
   }
@@ -1259,11 +1278,13 @@ std::string run_bench(const CliConfig& c) { return run_bench_impl(c); }
 
 AppReport run_app(const CliConfig& c, JobCache* cache) {
   AppReport r;
-  if (c.frames > 1 || c.decimate > 1) {
+  if (c.frames > 1 || c.decimate > 1 || c.unsharp_k > 0) {
     // (--decimate above 1 takes the frames path for one frame too: its hip
-    // branch downloads through the batch engine's one decimation launch)
-    PCONV_CHECK(cache == nullptr, c.frames > 1 ? "the resident service runs one image per job (--frames 1)"
-                                               : "the resident service runs no decimated job (--decimate 1)");
+    // branch downloads through the batch engine's one decimation launch; so
+    // does --unsharp, for the batch engine's snapshot and one unsharp launch)
+    PCONV_CHECK(cache == nullptr, c.frames > 1     ? "the resident service runs one image per job (--frames 1)"
+                                  : c.decimate > 1 ? "the resident service runs no decimated job (--decimate 1)"
+                                                   : "the resident service runs no unsharp job (no --unsharp)");
     r = run_frames(c);
     r.gpus = c.backend == Backend::Hip ? 1 : 0;
   } else if (c.backend == Backend::Auto && cache == nullptr && c.checkpoint_every == 0 && c.converge_every == 0) {
@@ -1317,6 +1338,8 @@ std::string report_json(const CliConfig& c, const AppReport& r) {
   if (c.decimate > 1)  // (the rates above still count input pixels)
     os << ", \"decimate\": " << c.decimate << ", \"out_width\": " << decimated_extent(c.width, c.decimate)
        << ", \"out_height\": " << decimated_extent(c.height, c.decimate);
+  if (c.unsharp_k > 0)  // (the amount k / 16: a multiple of 1/16 prints exactly)
+    os << ", \"unsharp\": " << c.unsharp_k / 16.0 << ", \"unsharp_threshold\": " << c.unsharp_threshold;
   if (!r.phases.empty()) {
     os << ", \"phases_s\": {";
     for (size_t i = 0; i < r.phases.size(); ++i)

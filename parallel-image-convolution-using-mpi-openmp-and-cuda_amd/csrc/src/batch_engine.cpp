@@ -5,6 +5,7 @@
 #include <cstring>
 #include <string>
 
+#include "pconv/cpu_stencil.hpp"
 #include "pconv/schedule.hpp"
 #include "pconv/trace.hpp"
 
@@ -135,6 +136,7 @@ void BatchEngine::upload_active(const std::vector<int32_t>& table) {
 void BatchEngine::upload(const uint8_t* p, int n, bool device) {
   sizes_.clear();  // back to uniform launches
   dims_host_.clear();
+  orig_n_ = 0;  // a snapshot describes the frames before this upload
   check_n("BatchEngine::upload", n);
   PCONV_CHECK(p != nullptr || n == 0, "BatchEngine::upload: null source");
   copy_images(true, const_cast<uint8_t*>(p), n, nullptr, device);
@@ -149,6 +151,7 @@ void BatchEngine::download(uint8_t* p, int n, bool device) {
 void BatchEngine::upload_sized(const uint8_t* p, const std::vector<ImageSize>& sizes, bool device) {
   std::vector<ImageDims> table = image_dims_table(geom_, capacity_, sizes);
   PCONV_CHECK(p != nullptr || sizes.empty(), "BatchEngine::upload_sized: null source");
+  orig_n_ = 0;
   if (!sizes.empty()) {
     stage(dims_, "extents", table.data(), sizeof(ImageDims), table.size());
     // No frame is cleared: the kernels read nothing outside an image.
@@ -242,6 +245,52 @@ int64_t decimated_packed_bytes(const ImageGeom& env, const std::vector<ImageSize
   for (const auto& z : sizes)
     total += decimated_extent(z.width, factor) * decimated_extent(z.height, factor) * env.pixel_bytes();
   return total;
+}
+
+// ---- unsharp mask -------------------------------------------------------------
+// The originals live in a third allocation laid out like the two frame sets
+// (image b at b * stride_, rows at lay_.pitch), so the kernel takes one stride
+// for all three pointers.  ONE launch each: the frames sit a whole number of
+// pitches apart, so images [0, n) are one pitched run of rows for the copy
+// (the ghost rows between them travel along), and the kernel takes `frames`.
+
+void BatchEngine::snapshot_original(int n) {
+  check_n("BatchEngine::snapshot_original", n);
+  PCONV_CHECK(active_host_.empty(), "BatchEngine::snapshot_original: an active-image table is in force");
+  PCONV_CHECK(!stream_capturing(cs_), "BatchEngine::snapshot_original: not captured into a hipGraph");
+  orig_n_ = 0;
+  if (n == 0) return;
+  if (!orig_.data()) orig_ = DeviceBuffer(static_cast<size_t>(stride_ * capacity_));
+  const int64_t rows = (n - 1) * (stride_ / lay_.pitch) + lay_.rows;
+  launch_copy_rows(frame_at(cur_), lay_.pitch, orig_.data() + lay_.offset(0), lay_.pitch, lay_.row_bytes, rows, cs_);
+  orig_n_ = n;
+}
+
+void BatchEngine::apply_unsharp(int k, int threshold, int n) {
+  check_n("BatchEngine::apply_unsharp", n);
+  check_unsharp(k, threshold, geom_.depth);
+  PCONV_CHECK(active_host_.empty(), "BatchEngine::apply_unsharp: an active-image table is in force");
+  PCONV_CHECK(!stream_capturing(cs_), "BatchEngine::apply_unsharp: not captured into a hipGraph");
+  PCONV_CHECK(n == orig_n_, "BatchEngine::apply_unsharp: " + std::to_string(n) + " images, but the snapshot holds " +
+                                std::to_string(orig_n_) + " (snapshot_original(n) after the upload, before run())");
+  orig_n_ = 0;  // the frames are no blur of the snapshot any more
+  if (n == 0) return;
+  UnsharpLaunch u;
+  u.orig = orig_.data() + lay_.offset(0);
+  u.blur = u.dst = frame_at(cur_);  // in place on the newest frames
+  u.orig_pitch = u.blur_pitch = u.dst_pitch = lay_.pitch;
+  u.row_bytes = lay_.row_bytes;
+  u.rows = lay_.rows;
+  u.depth = geom_.depth;
+  u.k = k;
+  u.threshold = threshold;
+  u.frames = n;
+  u.orig_stride = u.blur_stride = u.dst_stride = stride_;
+  if (!sizes_.empty()) {
+    u.dims = reinterpret_cast<const ImageDims*>(dims_.dev.data());
+    u.dims_host = dims_host_.data();
+  }
+  launch_unsharp(u, cs_);
 }
 
 // What every launch over images [0, n) of the current frames shares: whole

@@ -1,6 +1,8 @@
 // CLI parsing (see cli.hpp).
 #include "pconv/cli.hpp"
 
+#include "pconv/cpu_stencil.hpp"
+
 #include <cerrno>
 #include <climits>
 #include <cstdlib>
@@ -64,6 +66,15 @@ std::string help_text(const std::string& prog) {
          "                            --fuse, --frames, --depth 16, --synthetic, --out, --kernel.  Not with\n"
          "                            --gpus > 1, --server, --bench, --backend auto, --converge-every,\n"
          "                            --checkpoint-every, --graph\n"
+         "  --unsharp A               unsharp mask: the output is x + A (x - blur(x)) per sample, rounded to\n"
+         "                            nearest and clamped, x the input and blur(x) the run's result; A a decimal,\n"
+         "                            an exact multiple of 1/16 in [0.0625, 15.9375].  hip: the original stays on\n"
+         "                            the device, one extra copy and one pointwise launch.  --backend hip (1 GPU)\n"
+         "                            | cpu | omp, with --border, --filter, --fuse, --frames, --depth 16,\n"
+         "                            --synthetic, --out, --kernel.  Not with --gpus > 1, --server, --bench,\n"
+         "                            --backend auto, --converge-every, --checkpoint-every, --graph, --decimate > 1\n"
+         "  --unsharp-threshold T     with --unsharp: samples with |x - blur(x)| < T keep x (an integer in\n"
+         "                            [0, 255], depth 16: [0, 65535]; default 0: every sample is sharpened)\n"
          "  --check                   verify the result against the CPU oracle\n"
          "  --json                    print a JSON metrics line\n"
          "  --threads N               OpenMP threads for --backend omp\n"
@@ -172,6 +183,15 @@ CliConfig parse_cli(const std::vector<std::string>& args) {
       c.frames = static_cast<int>(parse_int(next("--frames"), "--frames", 1, 1 << 20));
     } else if (a == "--decimate") {
       c.decimate = static_cast<int>(parse_int(next("--decimate"), "--decimate", 1, kMaxDecimate));
+    } else if (a == "--unsharp") {
+      const std::string v = next("--unsharp");
+      char* end = nullptr;
+      const double amount = std::strtod(v.c_str(), &end);
+      if (v.empty() || *end != '\0') PCONV_FAIL("invalid --unsharp '" + v + "': a decimal multiple of 1/16");
+      c.unsharp_k = unsharp_k(amount);
+    } else if (a == "--unsharp-threshold") {
+      c.unsharp_threshold = parse_int(next("--unsharp-threshold"), "--unsharp-threshold", 0, 65535);
+      c.unsharp_threshold_set = true;
     } else if (a == "--check") {
       c.check = true;
     } else if (a == "--json") {
@@ -294,6 +314,19 @@ CliConfig parse_cli(const std::vector<std::string>& args) {
     if (c.converge_every > 0) refuse("--converge-every");
     if (c.checkpoint_every > 0) refuse("--checkpoint-every");
     if (c.graph) refuse("--graph (the decimated download is not captured into a hipGraph)");
+  }
+  if (c.unsharp_threshold_set && c.unsharp_k == 0) PCONV_FAIL("--unsharp-threshold needs --unsharp");
+  if (c.unsharp_k > 0) {
+    const auto refuse = [](const std::string& what) { PCONV_FAIL("--unsharp cannot be combined with " + what); };
+    check_unsharp(c.unsharp_k, c.unsharp_threshold, c.depth);
+    if (c.gpus > 1) refuse("--gpus above 1");
+    if (!c.server.empty()) refuse("--server");
+    if (c.bench_steps > 0) refuse("--bench");
+    if (c.backend == Backend::Auto) refuse("--backend auto");
+    if (c.converge_every > 0) refuse("--converge-every");
+    if (c.checkpoint_every > 0) refuse("--checkpoint-every");
+    if (c.graph) refuse("--graph (the unsharp launch is not captured into a hipGraph)");
+    if (c.decimate > 1) refuse("--decimate above 1 (sharpen after downscaling, not before)");
   }
   if (c.emulate_world > 0 && (c.bench_steps == 0 || c.gpus != 1))
     PCONV_FAIL("--emulate needs --bench and --gpus 1 (one process times one rank of the split)");

@@ -9,6 +9,10 @@
 #include <sched.h>
 
 #include <algorithm>
+#include <cmath>
+#include <limits>
+#include <sstream>
+#include <string>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -489,6 +493,76 @@ void cpu_convolve(const Filter& f, const ImageGeom& geom, const uint8_t* in, uin
   TeamScope team(be, threads);
   for (int t = 0; t < reps; ++t) fr.step();
   fr.copy_out_decimated(out, decimate);
+}
+
+// ---- unsharp mask --------------------------------------------------------------
+
+int unsharp_k(double amount) {
+  const double k = amount * 16.0;
+  std::ostringstream got;
+  got << amount;
+  PCONV_CHECK(k >= 1.0 && k <= 255.0 && k == std::floor(k),
+              "unsharp amount must be a multiple of 1/16 in [0.0625, 15.9375], got " + got.str());
+  return static_cast<int>(k);
+}
+
+void check_unsharp(int k, int64_t threshold, int depth) {
+  PCONV_CHECK(k >= 1 && k <= 255,
+              "unsharp amount must be a multiple of 1/16 in [0.0625, 15.9375], got " + std::to_string(k) + "/16");
+  const int64_t mx = depth == 16 ? 65535 : 255;
+  PCONV_CHECK(threshold >= 0 && threshold <= mx, "unsharp threshold must be an integer in [0, " + std::to_string(mx) +
+                                                     "], got " + std::to_string(threshold));
+}
+
+namespace {
+
+template <typename T>
+void unsharp_rows(const T* x, const T* b, T* out, int64_t n, int k, int t, bool omp) {
+  constexpr int32_t mx = std::numeric_limits<T>::max();
+#pragma omp parallel for schedule(static) if (omp)
+  for (int64_t i = 0; i < n; ++i) {
+    const int32_t xs = x[i], bs = b[i], d = xs - bs;
+    // floor(num / 16), what the kernel's arithmetic >> 4 gives, written without
+    // shifting a negative value
+    const int32_t num = xs * (16 + k) - bs * k + 8;
+    const int32_t q = num >= 0 ? num / 16 : -((-num + 15) / 16);
+    out[i] = static_cast<T>((d < 0 ? -d : d) < t ? xs : std::min(std::max(q, int32_t(0)), mx));
+  }
+}
+
+}  // namespace
+
+void cpu_unsharp(const ImageGeom& geom, const uint8_t* orig, const uint8_t* blurred, uint8_t* out, int k,
+                 int threshold, CpuBackend be, int threads) {
+  geom.validate();
+  check_unsharp(k, threshold, geom.depth);
+  TeamScope team(be, threads);
+  const bool omp = be == CpuBackend::OpenMP;
+  const int64_t n = geom.bytes() / (geom.depth / 8);
+  if (geom.depth == 16) {
+    // the callers' buffers are uint16 arrays: 2-byte aligned
+    PCONV_CHECK(reinterpret_cast<uintptr_t>(orig) % 2 == 0 && reinterpret_cast<uintptr_t>(blurred) % 2 == 0 &&
+                    reinterpret_cast<uintptr_t>(out) % 2 == 0,
+                "cpu_unsharp: depth 16 buffers must be 2-byte aligned");
+    unsharp_rows(reinterpret_cast<const uint16_t*>(orig), reinterpret_cast<const uint16_t*>(blurred),
+                 reinterpret_cast<uint16_t*>(out), n, k, threshold, omp);
+  } else {
+    unsharp_rows(orig, blurred, out, n, k, threshold, omp);
+  }
+}
+
+void cpu_unsharp_convolve(const Filter& f, const ImageGeom& geom, const uint8_t* in, uint8_t* out, int reps, int k,
+                          int threshold, CpuBackend be, int threads, Border border) {
+  check_unsharp(k, threshold, geom.depth);
+  if (out == in) {
+    // in place: the blurred image needs a buffer of its own beside the original
+    std::vector<uint8_t> blurred(static_cast<size_t>(geom.bytes()));
+    cpu_convolve(f, geom, in, blurred.data(), reps, be, threads, border);
+    cpu_unsharp(geom, in, blurred.data(), out, k, threshold, be, threads);
+    return;
+  }
+  cpu_convolve(f, geom, in, out, reps, be, threads, border);
+  cpu_unsharp(geom, in, out, out, k, threshold, be, threads);
 }
 
 uint64_t cpu_image_residual(const Filter& f, const ImageGeom& geom, const uint8_t* in, CpuBackend be, int threads,

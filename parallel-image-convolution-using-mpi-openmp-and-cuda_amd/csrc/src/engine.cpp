@@ -3,6 +3,7 @@
 
 #include <cstring>
 
+#include "pconv/cpu_stencil.hpp"
 #include "pconv/trace.hpp"
 
 #include <algorithm>
@@ -120,6 +121,7 @@ void BandEngine::upload_rows(const uint8_t* host, int64_t host_pitch, int64_t r_
   // Rows beyond the global image edge must stay zero.
   PCONV_CHECK(band_.y0 + r_begin >= 0 && band_.y0 + r_end <= geom_.height, "upload_rows: rows outside image");
   if (r_end == r_begin) return;
+  orig_valid_ = false;  // a snapshot describes the frame before this upload
   if (opt_.kernel_copies) {
     launch_copy_rows(host, host_pitch, src_frame() + r_begin * lay_.pitch, lay_.pitch, lay_.row_bytes,
                      r_end - r_begin, stream ? stream : cs_);
@@ -134,6 +136,7 @@ void BandEngine::upload_rows_device(const uint8_t* dev, int64_t dev_pitch, int64
               "upload_rows_device: rows outside frame");
   PCONV_CHECK(band_.y0 + r_begin >= 0 && band_.y0 + r_end <= geom_.height, "upload_rows_device: rows outside image");
   if (r_end == r_begin) return;
+  orig_valid_ = false;
   PCONV_HIP_CHECK(hipMemcpy2DAsync(src_frame() + r_begin * lay_.pitch, lay_.pitch, dev, dev_pitch, lay_.row_bytes,
                                    r_end - r_begin, hipMemcpyDeviceToDevice, cs_));
 }
@@ -242,6 +245,38 @@ void BandEngine::upload_decimated_from(const BandEngine& src, int factor) {
   // The frame's pads and ghost rows keep their zeros: the kernel writes
   // [0, row_bytes) of rows [0, rows) only (dst_bytes ends with the last row).
   src.launch_band_decimate(src_frame(), lay_.pitch, (lay_.rows - 1) * lay_.pitch + lay_.row_bytes, factor, cs_);
+  halo_valid_ = false;
+}
+
+// ---- unsharp mask -----------------------------------------------------------
+
+void BandEngine::snapshot_original() {
+  PCONV_CHECK(band_.y0 == 0 && band_.rows == geom_.height,
+              "snapshot_original: whole images only (the row bands of BandPipeline, LocalCluster and DistributedBlur "
+              "run no unsharp mask)");
+  PCONV_CHECK(!stream_capturing(cs_), "snapshot_original: not captured into a hipGraph");
+  const size_t need = static_cast<size_t>(lay_.rows * lay_.pitch);
+  if (orig_.size() < need) orig_ = DeviceBuffer(need);
+  launch_copy_rows(src_frame(), lay_.pitch, orig_.data(), lay_.pitch, lay_.row_bytes, lay_.rows, cs_);
+  orig_valid_ = true;
+}
+
+void BandEngine::apply_unsharp(int k, int threshold) {
+  check_unsharp(k, threshold, geom_.depth);
+  PCONV_CHECK(orig_valid_, "apply_unsharp: no original (snapshot_original() after the upload, before run())");
+  PCONV_CHECK(!stream_capturing(cs_), "apply_unsharp: not captured into a hipGraph");
+  UnsharpLaunch u;
+  u.orig = orig_.data();
+  u.orig_pitch = lay_.pitch;
+  u.blur = u.dst = src_frame();  // in place on the newest frame: pads and ghost rows keep their bytes
+  u.blur_pitch = u.dst_pitch = lay_.pitch;
+  u.row_bytes = lay_.row_bytes;
+  u.rows = lay_.rows;
+  u.depth = geom_.depth;
+  u.k = k;
+  u.threshold = threshold;
+  launch_unsharp(u, cs_);
+  orig_valid_ = false;   // the frame is no blur of the snapshot any more
   halo_valid_ = false;
 }
 

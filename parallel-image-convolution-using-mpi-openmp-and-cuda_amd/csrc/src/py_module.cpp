@@ -205,6 +205,41 @@ PYBIND11_MODULE(_pconv_native, m) {
       py::arg("filter") = "gaussian", py::arg("omp") = false, py::arg("threads") = 0, py::arg("border") = "zero",
       py::arg("depth") = 8, py::arg("decimate") = 1);
   m.attr("MAX_DECIMATE") = kMaxDecimate;
+  m.def(
+      "cpu_unsharp",
+      [](py::buffer orig, py::buffer blurred, py::buffer out, int64_t w, int64_t h, const std::string& ch, int k,
+         int64_t threshold, bool omp, int threads, int depth) {
+        const ImageGeom g = make_geom(w, h, ch, depth);
+        const HostView a = host_view(orig, false), b = host_view(blurred, false), c = host_view(out, true);
+        PCONV_CHECK(a.size == g.bytes() && b.size == g.bytes() && c.size == g.bytes(),
+                    "buffer size does not match the image geometry");
+        check_unsharp(k, threshold, depth);
+        py::gil_scoped_release nogil;
+        cpu_unsharp(g, a.ptr, b.ptr, c.ptr, k, static_cast<int>(threshold),
+                    omp ? CpuBackend::OpenMP : CpuBackend::Serial, threads);
+      },
+      py::arg("orig"), py::arg("blurred"), py::arg("dst"), py::arg("width"), py::arg("height"), py::arg("channels"),
+      py::arg("k"), py::arg("threshold") = 0, py::arg("omp") = false, py::arg("threads") = 0, py::arg("depth") = 8,
+      "Unsharp mask of two tight images: dst = x + (k / 16)(x - b) per sample, exact integers (dst may be blurred).");
+  m.def(
+      "cpu_unsharp_convolve",
+      [](py::buffer in, py::buffer out, int64_t w, int64_t h, const std::string& ch, int reps, int k,
+         int64_t threshold, py::object filter, bool omp, int threads, const std::string& border, int depth) {
+        const ImageGeom g = make_geom(w, h, ch, depth);
+        const Border bd = parse_border(border);
+        const HostView a = host_view(in, false), b = host_view(out, true);
+        PCONV_CHECK(a.size == g.bytes() && b.size == g.bytes(), "buffer size does not match the image geometry");
+        check_unsharp(k, threshold, depth);
+        const Filter f = make_filter(filter);
+        py::gil_scoped_release nogil;
+        cpu_unsharp_convolve(f, g, a.ptr, b.ptr, reps, k, static_cast<int>(threshold),
+                             omp ? CpuBackend::OpenMP : CpuBackend::Serial, threads, bd);
+      },
+      py::arg("src"), py::arg("dst"), py::arg("width"), py::arg("height"), py::arg("channels"), py::arg("reps"),
+      py::arg("k"), py::arg("threshold") = 0, py::arg("filter") = "gaussian", py::arg("omp") = false,
+      py::arg("threads") = 0, py::arg("border") = "zero", py::arg("depth") = 8,
+      "cpu_convolve followed by cpu_unsharp against the input.");
+  m.def("unsharp_k", &unsharp_k, py::arg("amount"), "amount x 16 as an exact integer in [1, 255], or an error");
   m.def("default_cpu_threads", &default_cpu_threads,
         "OpenMP team size used when none is set: affinity CPUs capped by the cgroup quota, minus one");
   m.def(
@@ -612,6 +647,92 @@ PYBIND11_MODULE(_pconv_native, m) {
       "strides in one launch, dims / dims_ptr: their SOURCE extents; an active table is refused; synchronises the "
       "stream.  timed = k: k further launches of the same arguments, returns the ms of each (stream events).");
   m.attr("DECIMATE_BLOCK_ROWS") = kDecimateBlockRows;
+  m.def(
+      "launch_unsharp",
+      [](uintptr_t orig, int64_t orig_pitch, uintptr_t blur, int64_t blur_pitch, uintptr_t dst, int64_t dst_pitch,
+         int64_t row_bytes, int64_t rows, int depth, int k, int threshold, int frames, int64_t orig_stride,
+         int64_t blur_stride, int64_t dst_stride, uintptr_t stream, py::object dims, uintptr_t dims_ptr,
+         py::object active, uintptr_t active_ptr, int timed) {
+        UnsharpLaunch a;
+        a.orig = reinterpret_cast<const uint8_t*>(orig);
+        a.orig_pitch = orig_pitch;
+        a.blur = reinterpret_cast<const uint8_t*>(blur);
+        a.blur_pitch = blur_pitch;
+        a.dst = reinterpret_cast<uint8_t*>(dst);
+        a.dst_pitch = dst_pitch;
+        a.row_bytes = row_bytes;
+        a.rows = rows;
+        a.depth = depth;
+        a.k = k;
+        a.threshold = threshold;
+        a.frames = frames;
+        a.orig_stride = orig_stride;
+        a.blur_stride = blur_stride;
+        a.dst_stride = dst_stride;
+        std::vector<ImageDims> dims_host;
+        if (!dims.is_none()) {
+          for (const auto& d : dims.cast<std::vector<std::pair<int32_t, int32_t>>>())
+            dims_host.push_back(ImageDims{d.first, d.second});
+          PCONV_CHECK(static_cast<int64_t>(dims_host.size()) == frames,
+                      "dims: the list must hold `frames` (row_bytes, height) pairs");
+          a.dims_host = dims_host.data();
+        }
+        a.dims = reinterpret_cast<const ImageDims*>(dims_ptr);
+        std::vector<int32_t> active_host;
+        if (!active.is_none()) {
+          active_host = active.cast<std::vector<int32_t>>();
+          a.active_host = active_host.data();
+        }
+        a.active = reinterpret_cast<const int32_t*>(active_ptr);
+        hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+        std::vector<double> ms;
+        py::gil_scoped_release nogil;
+        launch_unsharp(a, s);
+        // diagnostics: `timed` more launches, each between two timing events on the stream
+        std::vector<Event> ev;
+        for (int i = 0; i < 2 * timed; ++i) ev.push_back(Event::create(true));
+        for (int i = 0; i < timed; ++i) {
+          ev[2 * i].record(s);
+          launch_unsharp(a, s);
+          ev[2 * i + 1].record(s);
+        }
+        PCONV_HIP_CHECK(hipStreamSynchronize(s));
+        for (int i = 0; i < timed; ++i) ms.push_back(Event::elapsed_ms(ev[2 * i], ev[2 * i + 1]));
+        return ms;
+      },
+      py::arg("orig"), py::arg("orig_pitch"), py::arg("blur"), py::arg("blur_pitch"), py::arg("dst"),
+      py::arg("dst_pitch"), py::arg("row_bytes"), py::arg("rows"), py::arg("depth") = 8, py::arg("k") = 16,
+      py::arg("threshold") = 0, py::arg("frames") = 1, py::arg("orig_stride") = 0, py::arg("blur_stride") = 0,
+      py::arg("dst_stride") = 0, py::arg("stream") = 0, py::arg("dims") = py::none(), py::arg("dims_ptr") = 0,
+      py::arg("active") = py::none(), py::arg("active_ptr") = 0, py::arg("timed") = 0,
+      "Unsharp-mask kernel on raw pointers: dst = x + (k / 16)(x - b) per sample of three pitched frames (dst may "
+      "be blur: in place); `frames` frames at the three strides in one launch, dims / dims_ptr: their extents; an "
+      "active table is refused; synchronises the stream.  timed = n: n further launches of the same arguments "
+      "(out of place only: in place they would sharpen again), returns the ms of each (stream events).");
+  m.attr("UNSHARP_BLOCK_ROWS") = kUnsharpBlockRows;
+  m.def(
+      "time_copy_rows",
+      [](uintptr_t src, int64_t sp, uintptr_t dst, int64_t dp, int64_t row_bytes, int64_t rows, int timed) {
+        const uint8_t* s = reinterpret_cast<const uint8_t*>(src);
+        uint8_t* d = reinterpret_cast<uint8_t*>(dst);
+        py::gil_scoped_release nogil;
+        std::vector<Event> ev;
+        for (int i = 0; i < 2 * timed; ++i) ev.push_back(Event::create(true));
+        launch_copy_rows(s, sp, d, dp, row_bytes, rows, nullptr);
+        for (int i = 0; i < timed; ++i) {
+          ev[2 * i].record(nullptr);
+          launch_copy_rows(s, sp, d, dp, row_bytes, rows, nullptr);
+          ev[2 * i + 1].record(nullptr);
+        }
+        PCONV_HIP_CHECK(hipStreamSynchronize(nullptr));
+        std::vector<double> ms;
+        for (int i = 0; i < timed; ++i) ms.push_back(Event::elapsed_ms(ev[2 * i], ev[2 * i + 1]));
+        return ms;
+      },
+      py::arg("src"), py::arg("src_pitch"), py::arg("dst"), py::arg("dst_pitch"), py::arg("row_bytes"),
+      py::arg("rows"), py::arg("timed") = 0,
+      "Diagnostics: the row-copy kernel between two pitched device buffers, one launch and `timed` timed ones "
+      "(stream events on the default stream); the ms of each.");
   m.def("set_swar_shape", &set_swar_shape, py::arg("lw") = 0, py::arg("m") = 0, py::arg("nw") = 0,
         "Force the SWAR temporal tile shape (lw=0: back to the latency model).");
   m.def("swar_shapes", []() {
@@ -836,6 +957,10 @@ PYBIND11_MODULE(_pconv_native, m) {
       .def("decimated_row_bytes", &BandEngine::decimated_row_bytes, py::arg("factor"))
       .def("upload_decimated_from", &BandEngine::upload_decimated_from, py::arg("src"), py::arg("factor"),
            "src's newest frame, decimated, becomes this engine's current frame (device to device, one launch)")
+      .def("snapshot_original", &BandEngine::snapshot_original,
+           "copy the current frame's owned rows into the engine's third device buffer (after the upload, before run)")
+      .def("apply_unsharp", &BandEngine::apply_unsharp, py::arg("k"), py::arg("threshold") = 0,
+           "newest frame = x + (k / 16)(x - newest frame), x the snapshot: one launch, in place")
       .def("set_halo_valid", &BandEngine::set_halo_valid)
       .def("wait_stream", [](BandEngine& e, uintptr_t s) { e.wait_stream(reinterpret_cast<hipStream_t>(s)); })
       .def("signal_stream", [](BandEngine& e, uintptr_t s) { e.signal_stream(reinterpret_cast<hipStream_t>(s)); })
@@ -1062,6 +1187,10 @@ PYBIND11_MODULE(_pconv_native, m) {
                                for (const auto& z : e.sizes()) out.emplace_back(z.width, z.height);
                                return out;
                              })
+      .def("snapshot_original", &BatchEngine::snapshot_original, py::arg("n"),
+           "copy the current frames' rows of images [0, n) into the engine's third allocation (ONE launch)")
+      .def("apply_unsharp", &BatchEngine::apply_unsharp, py::arg("k"), py::arg("threshold"), py::arg("n"),
+           "newest frames of images [0, n) = x + (k / 16)(x - newest), x the snapshot: ONE launch, in place")
       .def("wait_stream", [](BatchEngine& e, uintptr_t s) { e.wait_stream(reinterpret_cast<hipStream_t>(s)); })
       .def("signal_stream", [](BatchEngine& e, uintptr_t s) { e.signal_stream(reinterpret_cast<hipStream_t>(s)); })
       .def("run", &BatchEngine::run, py::arg("reps"), py::arg("n"), py::call_guard<py::gil_scoped_release>())

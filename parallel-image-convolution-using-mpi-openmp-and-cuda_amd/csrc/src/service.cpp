@@ -154,6 +154,7 @@ int serve_main(const ServeOptions& o) {
         PCONV_CHECK(c.server.empty(), "service: a job cannot name another server");
         PCONV_CHECK(c.depth == 8, "service: --depth 16 cannot run as a served job");
         PCONV_CHECK(c.decimate == 1, "service: --decimate above 1 cannot run as a served job");
+        PCONV_CHECK(c.unsharp_k == 0, "service: --unsharp cannot run as a served job");
         PCONV_CHECK(o.device >= 0 || c.backend != Backend::Hip, "service: this server has no GPU (--device -1)");
         const AppReport r = run_app(c, cache.get());
         reply = report_json(c, r);

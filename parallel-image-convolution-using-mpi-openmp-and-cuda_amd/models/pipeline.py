@@ -51,13 +51,15 @@ class FilterPipeline:
         return "FilterPipeline(" + ",".join(f"{s.filter.name}:{s.reps}" for s in self.stages) + ")"
 
     def apply(self, image, backend: str = "auto", device: Optional[int] = None, border: str = "zero",
-              decimate: int = 1):
+              decimate: int = 1, unsharp=None):
         """Run every stage in order (each under the same ``border`` rule); returns
         the same container type as ``image``.  ``decimate`` applies after the
-        last stage (``convolve``'s keyword)."""
-        from ..ops.reference import check_decimate, refuse_depth16
+        last stage (``convolve``'s keyword).  ``unsharp`` is refused by name
+        (the unsharp mask works on one image and one blur: ``pconv.unsharp``)."""
+        from ..ops.reference import check_decimate, refuse_depth16, refuse_unsharp
         from ..ops.stencil import convolve
 
+        refuse_unsharp("FilterPipeline", unsharp)
         refuse_depth16(image, "FilterPipeline")
         factor = check_decimate(decimate)
         out = image

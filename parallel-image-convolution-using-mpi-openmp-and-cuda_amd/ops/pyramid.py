@@ -13,7 +13,8 @@ written by the decimation kernel straight from the level above
 already decimated.  A CUDA tensor never touches the host.
 
 Out of scope: pyramids of batches, a phase other than 0, factors other than 2
-between levels, and any filtering other than the repetitions already run.
+between levels, any filtering other than the repetitions already run, and the
+unsharp mask (``unsharp=`` is refused by name: sharpen a level afterwards).
 """
 from __future__ import annotations
 
@@ -24,7 +25,7 @@ import numpy as np
 import torch
 
 from ..models.filters import get_filter
-from .reference import check_border
+from .reference import check_border, refuse_unsharp
 from .stencil import (_CH_COUNT, _NP_DTYPE, Engine, _bytes_of, _check_depth, _check_tensor_dtype, _host_samples,
                       _resolve_backend, convolve, image_depth, image_geometry)
 
@@ -61,7 +62,8 @@ class Pyramid:
     """
 
     def __init__(self, width: int, height: int, channels: str = "grey", levels: int = 1, reps: int = 2,
-                 filter="gaussian", border: str = "zero", device: int = 0, depth: int = 8):
+                 filter="gaussian", border: str = "zero", device: int = 0, depth: int = 8, unsharp=None):
+        refuse_unsharp("Pyramid", unsharp)
         if reps < 0:
             raise ValueError("reps must be >= 0")
         if channels not in _CH_COUNT:
@@ -149,7 +151,7 @@ def _cached_pyramid(w, h, ch, levels, reps, flt, border, device, depth) -> Pyram
 
 
 def pyramid(image, levels: int, reps: int = 2, filter="gaussian", border: str = "zero", backend: str = "auto",
-            device: Optional[int] = None) -> list:
+            device: Optional[int] = None, unsharp=None) -> list:
     """The ``levels`` levels of the pyramid of ``image``, a list: level 0 is the
     input itself, level k + 1 is ``convolve(level k, reps, filter,
     border=border, decimate=2)``.  ``levels`` may not exceed the number of
@@ -160,6 +162,7 @@ def pyramid(image, levels: int, reps: int = 2, filter="gaussian", border: str = 
     kept): one upload, the levels handed down on the device, one decimated
     download per level.  The other backends chain :func:`convolve` calls.
     """
+    refuse_unsharp("pyramid", unsharp)
     if reps < 0:
         raise ValueError("reps must be >= 0")
     flt = get_filter(filter)

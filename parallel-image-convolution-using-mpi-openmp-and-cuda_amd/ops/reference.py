@@ -122,6 +122,62 @@ def numpy_decimate(img: np.ndarray, s: int) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(img)[::s, ::s])
 
 
+def check_unsharp_amount(amount) -> int:
+    """``k = amount * 16`` of an unsharp mask: an exact integer in [1, 255]
+    (``ValueError`` otherwise; a sequence of amounts is refused by name)."""
+    if isinstance(amount, (list, tuple, dict, np.ndarray)) or hasattr(amount, "shape") and tuple(amount.shape):
+        raise ValueError("unsharp: per-channel amounts are not supported (one amount applies to every channel)")
+    bad = f"unsharp amount must be a multiple of 1/16 in [0.0625, 15.9375], got {amount!r}"
+    if isinstance(amount, bool) or not isinstance(amount, (int, float, np.integer, np.floating)):
+        raise ValueError(bad)
+    k = float(amount) * 16.0
+    if not (1.0 <= k <= 255.0) or k != int(k):
+        raise ValueError(bad)
+    return int(k)
+
+
+def refuse_unsharp(what: str, unsharp=None, threshold=0) -> None:
+    """The named error of everything the unsharp mask is not built for: raised
+    when a caller passes ``unsharp`` (or a threshold for it) to ``what``."""
+    if unsharp is not None or threshold not in (0, None):
+        raise ValueError(f"{what}: unsharp is not supported (use pconv.unsharp, Engine.unsharp or "
+                         f"BatchEngine.unsharp on the image itself)")
+
+
+def check_unsharp_threshold(threshold, depth: int) -> int:
+    """An unsharp threshold: an integer in [0, 255] (depth 16: [0, 65535])."""
+    top = 65535 if depth == 16 else 255
+    bad = f"unsharp threshold must be an integer in [0, {top}], got {threshold!r}"
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, np.integer)):
+        raise ValueError(bad)
+    if not 0 <= int(threshold) <= top:
+        raise ValueError(bad)
+    return int(threshold)
+
+
+def numpy_unsharp(img: np.ndarray, reps: int, amount=1.0, threshold=0, filt="gaussian",
+                  border: str = "zero") -> np.ndarray:
+    """Unsharp mask, ``x + amount * (x - blur(x))`` in exact integers.  With
+    ``b = numpy_convolve(img, reps, filt, border)``, ``k = amount * 16`` (an
+    integer in [1, 255]), ``t = threshold`` and ``max`` = 255 or 65535, per
+    sample (every channel alike)::
+
+        d   = x - b
+        out = x                                            if |d| < t
+        out = clamp((x (16 + k) - b k + 8) >> 4, 0, max)   otherwise
+
+    The shift is arithmetic (floor).  ``reps = 0`` returns the input."""
+    x = np.asarray(img, dtype=sample_dtype(img))
+    depth = 16 if x.dtype == np.uint16 else 8
+    k = check_unsharp_amount(amount)
+    t = check_unsharp_threshold(threshold, depth)
+    top = int(np.iinfo(x.dtype).max)
+    xs = x.astype(np.int64)
+    bs = numpy_convolve(x, reps, filt, border).astype(np.int64)
+    sharp = np.clip((xs * (16 + k) - bs * k + 8) >> 4, 0, top)
+    return np.where(np.abs(xs - bs) < t, xs, sharp).astype(x.dtype)
+
+
 def numpy_residual(img: np.ndarray, filt="gaussian", border: str = "zero") -> int:
     """Bytes of ``img`` that one more repetition would change; 0 means ``img``
     is a fixed point of the iterated map.  By definition

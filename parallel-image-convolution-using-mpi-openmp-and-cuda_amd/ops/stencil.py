@@ -25,8 +25,9 @@ import torch
 
 from .._native import require_native
 from ..models.filters import get_filter
-from .reference import (check_border, check_decimate, check_depth16_filter, decimated_shape, numpy_convolve,
-                        numpy_decimate, numpy_residual, numpy_step)
+from .reference import (check_border, check_decimate, check_depth16_filter, check_unsharp_amount,
+                        check_unsharp_threshold, decimated_shape, numpy_convolve, numpy_decimate, numpy_residual,
+                        numpy_step, numpy_unsharp, refuse_unsharp)
 
 _CHANNELS = {1: "grey", 3: "rgb", 4: "rgba"}
 _CH_COUNT = {"grey": 1, "rgb": 3, "rgba": 4}
@@ -143,6 +144,7 @@ class Engine:
             fuse = n.auto_fuse(nf, variant, int(width) * int(height) * ch * (self.depth // 8), ch, depth=self.depth)
         self.width, self.height, self.channels = int(width), int(height), channels
         self.device = int(device)
+        self.graph = bool(graph)
         self._eng = n.BandEngine(self.width, self.height, channels, nf, 0, 1, self.device, halo=int(fuse),
                                  fuse=int(fuse), overlap=True, graph=bool(graph), variant=variant,
                                  border=self.border, depth=self.depth)
@@ -206,6 +208,46 @@ class Engine:
         if isinstance(img, torch.Tensor):
             return self.run_tensor(img, reps, decimate)
         return self.run_numpy(np.asarray(img), reps, decimate)
+
+    # ---- unsharp mask --------------------------------------------------
+    def unsharp(self, img, reps: int, amount=1.0, threshold=0):
+        """``numpy_unsharp(img, reps, amount, threshold, ...)``: ``x + amount *
+        (x - blur(x))`` per sample, in exact integers.  The image is uploaded
+        once; one device copy keeps the original beside the frames, ``reps``
+        repetitions run as in ``__call__``, one pointwise launch combines the
+        two in place, and the sharpened frame is downloaded.  Same container
+        and device as ``img`` (a CUDA tensor never leaves the device)."""
+        k = check_unsharp_amount(amount)
+        t = check_unsharp_threshold(threshold, self.depth)
+        if int(reps) < 0:
+            raise ValueError("reps must be >= 0")
+        if self.graph:
+            raise ValueError("unsharp: hipGraph capture (graph=True) is not supported")
+        self._check_samples(img)
+        e = self._eng
+        if isinstance(img, torch.Tensor) and img.device.type == "cuda":
+            src = img.contiguous()
+            out = torch.empty_like(src)
+            ts = torch.cuda.current_stream(src.device).cuda_stream
+            e.wait_stream(ts)
+            e.upload_ptr(src.data_ptr(), self.row_bytes, 0, self.height, device=True)
+            e.snapshot_original()
+            e.run(int(reps))
+            e.apply_unsharp(k, t)
+            e.download_ptr(out.data_ptr(), self.row_bytes, 0, self.height, device=True)
+            e.signal_stream(ts)
+            src.record_stream(torch.cuda.current_stream(src.device))
+            return out
+        is_tensor = isinstance(img, torch.Tensor)
+        src = _host_samples(img, self.depth)
+        out = np.empty_like(src)
+        e.upload(_bytes_of(src), 0, self.height)
+        e.snapshot_original()
+        e.run(int(reps))
+        e.apply_unsharp(k, t)
+        e.download(_bytes_of(out), 0, self.height)
+        e.synchronize()
+        return torch.from_numpy(out) if is_tensor else out
 
     # ---- fixed point -------------------------------------------------
     def _with_frame(self, img, work):
@@ -353,6 +395,68 @@ def _resolve_backend(image, backend: str) -> str:
     return backend
 
 
+def _refuse_unsharp_decimate(decimate) -> None:
+    if decimate != 1:
+        raise ValueError("unsharp: decimate is not supported (thumbnail pipelines sharpen after downscaling, not "
+                         "before: decimate first, then sharpen the small image)")
+
+
+def unsharp(image, reps: int = 1, amount=1.0, threshold=0, filter="gaussian", backend: str = "auto",
+            device: Optional[int] = None, threads: int = 0, border: str = "zero", fuse: Optional[int] = None,
+            variant: str = "auto", decimate: int = 1):
+    """Unsharp mask: ``x + amount * (x - convolve(x, reps, filter, border))``
+    per sample, rounded to nearest and clamped, in exact integers — the
+    "sharpen" that goes with :func:`convolve`'s "blur".
+
+    ``amount``: a multiple of 1/16 in [0.0625, 15.9375] (one amount for every
+    channel, an RGBA image's fourth included).  ``threshold`` (an integer in
+    [0, 255], depth 16: [0, 65535]): samples whose difference to the blurred
+    image is below it keep their value.  The result is
+    ``numpy_unsharp(image, reps, amount, threshold, filter, border)`` on every
+    backend (``hip | omp | cpu | numpy | auto``), in the input's container and
+    on its device.  On ``hip`` the image is uploaded once, the original stays
+    on the device beside the frames, and one pointwise launch combines the two
+    before the download; a CUDA tensor never leaves the device.
+
+    Out of scope, refused by name: ``decimate`` above 1, per-channel amounts,
+    hipGraph capture, differences of two blurs.
+    """
+    if reps < 0:
+        raise ValueError("reps must be >= 0")
+    _refuse_unsharp_decimate(decimate)
+    flt = get_filter(filter)
+    check_border(border)
+    is_tensor = isinstance(image, torch.Tensor)
+    _check_tensor_dtype(image)
+    depth = image_depth(image)
+    k = check_unsharp_amount(amount)
+    t = check_unsharp_threshold(threshold, depth)
+    w, h, ch = image_geometry(tuple(image.shape))
+    backend = _resolve_backend(image, backend)
+    _check_depth(depth, flt, variant if backend == "hip" else "auto")
+
+    if backend == "numpy":
+        arr = image.cpu().numpy() if is_tensor else np.asarray(image)
+        out = numpy_unsharp(arr, reps, amount, t, flt, border)
+        return torch.from_numpy(out).to(image.device) if is_tensor else out
+
+    if backend in ("cpu", "omp"):
+        arr = _host_samples(image, depth)
+        out = np.empty_like(arr)
+        require_native().cpu_unsharp_convolve(_bytes_of(arr), _bytes_of(out), w, h, ch, int(reps), k, t,
+                                              flt.to_native(), backend == "omp", int(threads), border=border,
+                                              depth=depth)
+        return torch.from_numpy(out).to(image.device) if is_tensor else out
+
+    if device is None:
+        device = image.device.index if (is_tensor and image.is_cuda) else 0
+    eng = _cached_engine(w, h, ch, flt, int(device or 0), fuse, False, variant, border, depth)
+    return eng.unsharp(image, reps, amount, t)
+
+
+_unsharp = unsharp  # (convolve_file's keyword of the same name shadows the function there)
+
+
 def residual(image, filter="gaussian", backend: str = "auto", device: Optional[int] = None, threads: int = 0,
              border: str = "zero") -> int:
     """Bytes of ``image`` that one more repetition of ``filter`` would change
@@ -378,7 +482,8 @@ def residual(image, filter="gaussian", backend: str = "auto", device: Optional[i
 
 def convolve_until_stable(image, max_reps: int, filter="gaussian", check_every: Optional[int] = None,
                           backend: str = "auto", device: Optional[int] = None, fuse: Optional[int] = None,
-                          graph: bool = False, variant: str = "auto", threads: int = 0, border: str = "zero"):
+                          graph: bool = False, variant: str = "auto", threads: int = 0, border: str = "zero",
+                          unsharp=None):
     """``convolve`` that stops at the fixed point of the iterated map.
 
     Runs chunks of ``check_every`` repetitions (the last one shorter; default
@@ -388,6 +493,7 @@ def convolve_until_stable(image, max_reps: int, filter="gaussian", check_every: 
     repetition returns the same bytes, so a converged result equals
     ``convolve(image, max_reps, ...)``.  Returns ``(out, StableInfo)``.
     """
+    refuse_unsharp("convolve_until_stable", unsharp)
     _check_stable_args(max_reps, check_every)
     flt = get_filter(filter)
     check_border(border)
@@ -641,6 +747,37 @@ class BatchEngine:
         s = check_decimate(decimate)
         return self._with_images(images, lambda n: self._eng.run(int(reps), n), s)[0]
 
+    # ---- unsharp mask --------------------------------------------------
+    def _unsharp_work(self, reps, amount, threshold):
+        """The work between a call's upload and download: one copy launch keeps
+        all originals on the device, the repetitions, one unsharp launch."""
+        k = check_unsharp_amount(amount)
+        t = check_unsharp_threshold(threshold, self.depth)
+        if int(reps) < 0:
+            raise ValueError("reps must be >= 0")
+        e = self._eng
+
+        def work(n):
+            e.snapshot_original(n)
+            e.run(int(reps), n)
+            e.apply_unsharp(k, t, n)
+
+        return work
+
+    def unsharp(self, stack, reps: int, amount=1.0, threshold=0):
+        """:meth:`Engine.unsharp` of every image of a stack: entry b equals
+        ``numpy_unsharp(stack[b], reps, amount, threshold, ...)``.  One upload,
+        ONE copy launch for all originals, the fused launches of ``__call__``,
+        ONE unsharp launch, one download."""
+        work = self._unsharp_work(reps, amount, threshold)
+        return self._with_frames(stack if isinstance(stack, torch.Tensor) else np.asarray(stack), work)[0]
+
+    def unsharp_images(self, images, reps: int, amount=1.0, threshold=0) -> list:
+        """:meth:`unsharp` for a sequence of images of any sizes within the
+        envelope (:meth:`run_images`' inputs): the unsharp launch reads the
+        upload's extents table, so every image is sharpened as a lone one."""
+        return self._with_images(images, self._unsharp_work(reps, amount, threshold))[0]
+
     def residual_images(self, images=None) -> np.ndarray:
         """:meth:`residual` for mixed sizes: of ``images``, or (``None``) of the
         frames the engine holds after its last mixed-size call."""
@@ -797,10 +934,43 @@ def convolve_batch(images, reps: int = 1, filter="gaussian", backend: str = "aut
     return torch.cat(outs) if is_tensor else np.concatenate(outs)
 
 
+def unsharp_batch(images, reps: int = 1, amount=1.0, threshold=0, filter="gaussian", backend: str = "auto",
+                  device: Optional[int] = None, fuse: Optional[int] = None, variant: str = "auto", threads: int = 0,
+                  border: str = "zero", batch_size: Optional[int] = None, decimate: int = 1):
+    """:func:`unsharp` for N same-size images at once (:func:`convolve_batch`'s
+    inputs, engine cache, chunking and ``batch_size``): the result equals
+    ``np.stack([unsharp(img, reps, amount, threshold, ...) for img in
+    images])`` on every backend.  ``hip``: per chunk one copy launch for the
+    originals and one unsharp launch beside the fused launches; the other
+    backends loop over the images."""
+    if reps < 0:
+        raise ValueError("reps must be >= 0")
+    _refuse_unsharp_decimate(decimate)
+    flt, stack, is_tensor, geo, backend = _prepare_batch(images, filter, backend, border, batch_size)
+    depth = image_depth(stack)
+    check_unsharp_amount(amount)
+    t = check_unsharp_threshold(threshold, depth)
+    _check_depth(depth, flt, variant if backend == "hip" else "auto")
+    n_img = int(stack.shape[0])
+    if n_img == 0:
+        return _empty_like_stack(stack, is_tensor)
+
+    if backend != "hip":
+        outs = [unsharp(stack[i], reps, amount, t, flt, backend=backend, threads=threads, border=border)
+                for i in range(n_img)]
+        return torch.stack(outs) if is_tensor else np.stack(outs)
+
+    eng, cap = _hip_batch_engine(stack, is_tensor, geo, flt, device, fuse, variant, border, batch_size)
+    if n_img <= cap:
+        return eng.unsharp(stack, reps, amount, t)
+    outs = [eng.unsharp(stack[i:i + cap], reps, amount, t) for i in range(0, n_img, cap)]
+    return torch.cat(outs) if is_tensor else np.concatenate(outs)
+
+
 def convolve_batch_until_stable(images, max_reps: int, filter="gaussian", check_every: Optional[int] = None,
                                 backend: str = "auto", device: Optional[int] = None, fuse: Optional[int] = None,
                                 variant: str = "auto", threads: int = 0, border: str = "zero",
-                                batch_size: Optional[int] = None, compact: bool = False):
+                                batch_size: Optional[int] = None, compact: bool = False, unsharp=None):
     """``convolve_until_stable`` for N same-size 8-bit images at once.
 
     Inputs, backends, the engine cache and ``batch_size`` are
@@ -819,6 +989,7 @@ def convolve_batch_until_stable(images, max_reps: int, filter="gaussian", check_
     image and already stop each image at its own fixed point.  The return
     values are identical for both settings on every backend.
     """
+    refuse_unsharp("convolve_batch_until_stable", unsharp)
     _check_stable_args(max_reps, check_every)
     flt, stack, is_tensor, geo, backend = _prepare_batch(images, filter, backend, border, batch_size)
     _refuse_depth16(stack, "convolve_batch_until_stable")
@@ -1000,10 +1171,40 @@ def convolve_many(images, reps: int = 1, filter="gaussian", backend: str = "auto
     return outs
 
 
+def unsharp_many(images, reps: int = 1, amount=1.0, threshold=0, filter="gaussian", backend: str = "auto",
+                 device: Optional[int] = None, fuse: Optional[int] = None, variant: str = "auto", threads: int = 0,
+                 border: str = "zero", batch_size: Optional[int] = None, min_fill: float = 0.5,
+                 decimate: int = 1) -> list:
+    """:func:`unsharp` for a sequence of images of ANY sizes
+    (:func:`convolve_many`'s inputs and size buckets): entry i equals
+    ``unsharp(images[i], reps, amount, threshold, ...)``; ``[]`` gives ``[]``.
+    ``hip``: per bucket one copy launch for the originals and one unsharp
+    launch, which reads the bucket's extents table."""
+    if reps < 0:
+        raise ValueError("reps must be >= 0")
+    _refuse_unsharp_decimate(decimate)
+    flt, seq, is_tensor, ch, backend = _prepare_many(images, filter, backend, border, batch_size, min_fill)
+    check_unsharp_amount(amount)
+    if not seq:
+        check_unsharp_threshold(threshold, 16)
+        return []
+    depth = image_depth(seq[0])
+    t = check_unsharp_threshold(threshold, depth)
+    _check_depth(depth, flt, variant if backend == "hip" else "auto")
+    if backend != "hip":
+        return [unsharp(im, reps, amount, t, flt, backend=backend, threads=threads, border=border) for im in seq]
+    outs = [None] * len(seq)
+    for eng, idx in _hip_buckets(seq, is_tensor, ch, flt, device, fuse, variant, border, batch_size, min_fill):
+        for i, o in zip(idx, eng.unsharp_images([seq[i] for i in idx], reps, amount, t)):
+            outs[i] = o
+    return outs
+
+
 def convolve_many_until_stable(images, max_reps: int, filter="gaussian", check_every: Optional[int] = None,
                                backend: str = "auto", device: Optional[int] = None, fuse: Optional[int] = None,
                                variant: str = "auto", threads: int = 0, border: str = "zero",
-                               batch_size: Optional[int] = None, min_fill: float = 0.5, compact: bool = False):
+                               batch_size: Optional[int] = None, min_fill: float = 0.5, compact: bool = False,
+                               unsharp=None):
     """``convolve_until_stable`` for a sequence of images of any sizes
     (:func:`convolve_many`'s inputs and buckets).  Returns ``([out],
     [StableInfo])``: entry i of both is what ``convolve_until_stable(images[i],
@@ -1012,6 +1213,7 @@ def convolve_many_until_stable(images, max_reps: int, filter="gaussian", check_e
     ``compact`` is :func:`convolve_batch_until_stable`'s, per bucket: same
     return values; the ``cpu`` and ``numpy`` backends accept and ignore it
     (they already stop each image at its own fixed point)."""
+    refuse_unsharp("convolve_many_until_stable", unsharp)
     _check_stable_args(max_reps, check_every)
     flt, seq, is_tensor, ch, backend = _prepare_many(images, filter, backend, border, batch_size, min_fill)
     if not seq:
@@ -1049,15 +1251,24 @@ def residual_many(images, filter="gaussian", backend: str = "auto", device: Opti
 
 def convolve_file(path: str, width: int, height: int, reps: int, channels: str = "grey", filter="gaussian",
                   out: Optional[str] = None, backend: str = "auto", device: Optional[int] = None,
-                  border: str = "zero", depth: int = 8, decimate: int = 1) -> str:
+                  border: str = "zero", depth: int = 8, decimate: int = 1, unsharp=None,
+                  unsharp_threshold=0) -> str:
     """The reference program in one call (``cuda/main.c:10-53``): read the raw
     image, ``reps`` repetitions, write ``blur_<name>`` (or ``out``); returns the
     output path.  ``decimate=s``: the file holds the decimated result,
-    ``ceil(height / s) x ceil(width / s)`` pixels."""
+    ``ceil(height / s) x ceil(width / s)`` pixels.  ``unsharp=amount`` (with
+    ``unsharp_threshold``): the file holds :func:`unsharp` of the image
+    instead of its blur (not together with ``decimate`` above 1)."""
     from ..utils.raw_io import output_path_for, read_raw, write_raw
 
+    if unsharp is None and unsharp_threshold not in (0, None):
+        raise ValueError("unsharp_threshold needs unsharp (an amount)")
     img = read_raw(path, width, height, channels, depth=depth)
-    res = convolve(img, reps, filter, backend=backend, device=device, border=border, decimate=decimate)
+    if unsharp is not None:
+        res = _unsharp(img, reps, unsharp, unsharp_threshold, filter, backend=backend, device=device, border=border,
+                       decimate=check_decimate(decimate))
+    else:
+        res = convolve(img, reps, filter, backend=backend, device=device, border=border, decimate=decimate)
     dst = out or output_path_for(path)
     write_raw(dst, res)
     return dst

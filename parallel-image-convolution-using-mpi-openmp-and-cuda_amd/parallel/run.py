@@ -107,7 +107,13 @@ def parse(argv: List[str]) -> argparse.Namespace:
                         "were steadier on a shared host, profiles/r03/hybrid/)")
     p.add_argument("--no-numa-bind", action="store_true",
                    help="--backend hip: leave each rank's CPU affinity alone (default: the GPU's NUMA node)")
+    p.add_argument("--unsharp", default=None, metavar="A",
+                   help="not supported here: the unsharp mask runs on one GPU or the CPU (conv --unsharp, "
+                        "pconv.unsharp)")
     a = p.parse_args(argv)
+    if a.unsharp is not None:
+        p.error("--unsharp is not supported by pconv.parallel.run (row bands keep no original: use conv --unsharp "
+                "on one GPU, or pconv.unsharp)")
     if a.width < 1 or a.height < 1 or a.reps < 0 or a.checkpoint_every < 0 or a.converge_every < 0:
         sys.stderr.write(usage(prog))
         raise SystemExit(1)
