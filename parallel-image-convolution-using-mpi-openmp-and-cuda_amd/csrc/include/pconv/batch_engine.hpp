@@ -175,14 +175,16 @@ class BatchEngine {
   void zero_words(uint8_t* p, size_t bytes);
   // One pitched copy per image between `packed` and the current frames.
   void copy_images(bool to_frames, uint8_t* packed, int n, const ImageDims* extents, bool device);
-  // The newest frames of images [0, n), decimated, into `packed`.
-  void decimate_images(uint8_t* packed, int n, int factor, const ImageDims* extents, bool device);
+  // The newest frames of images [0, n), decimated, into `packed` (in mixed
+  // mode each at its own decimated extent).
+  void decimate_images(uint8_t* packed, int n, int factor, bool device);
   DeviceBuffer dec_stage_;  // staging frames of the decimated envelope (first use, regrown)
   DeviceBuffer orig_;       // snapshot_original(): `capacity` frames laid out like frame_ (first use)
   int orig_n_ = 0;          // images the snapshot holds (0: none, or already consumed)
   // Rewrite `t` with n entries of entry_bytes each (`what` names it in errors).
   void stage(StagedTable& t, const char* what, const void* entries, size_t entry_bytes, size_t n);
   void upload_active(const std::vector<int32_t>& table);
+  ImageTables image_tables(int n) const;
   StencilLaunch base_launch(int n) const;
   void launch_batch_residual(int n);
   void enqueue_residual(int n);

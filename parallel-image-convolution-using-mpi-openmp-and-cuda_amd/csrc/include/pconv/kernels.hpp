@@ -30,21 +30,19 @@
 namespace pconv {
 
 // Extent of one image of a mixed-size batch inside its frame (device table of
-// the temporal and residual kernels, host copy for the guards): 8 bytes.
+// the kernels, host copy for the guards): 8 bytes.
 struct ImageDims {
   int32_t row_bytes;
   int32_t height;
 };
 
-// The images of one launch (temporal kernels and the residual kernel): which
-// frames exist, which of them the grid covers, and how much of each frame is
-// image.  Every other field of StencilLaunch describes ONE frame and applies
-// to each.
-//   frames / stride: `frames` frames of that geometry lie `stride` bytes apart,
-// in src and dst alike (the residual kernel's counters number the same); frame
-// b starts b * stride after frame 0.  More than one frame needs a 16-byte
-// aligned stride that holds a whole frame.  Images never read each other's
-// rows: the set only moves the base pointers.
+// The images of one launch: which frames exist, which of them the grid covers,
+// and how much of each frame is image.  Every other field of a launch struct
+// describes ONE frame and applies to each.  ImageTables is the part every
+// launch over frames shares (the pointwise launches carry it as it is, beside a
+// stride per operand); ImageSet adds the one stride of the temporal and
+// residual kernels.
+//   frames: frames of the launch's geometry, at the launch's stride(s).
 //   active / active_host / count: optional table of `count` strictly increasing
 // frame indices inside [0, frames).  With it the grid is `count` images wide
 // and its k-th image is frame active[k]; frames the table does not name are
@@ -63,9 +61,8 @@ struct ImageDims {
 // frames - 1 and to the envelope, so a wrong table stays inside the
 // allocation) plus the host copy of the same entries the guards and tuners
 // read; both pointers or neither.
-struct ImageSet {
+struct ImageTables {
   int frames = 1;
-  int64_t stride = 0;
   const int32_t* active = nullptr;
   const int32_t* active_host = nullptr;
   int count = 0;
@@ -79,6 +76,15 @@ struct ImageSet {
   int frame_of(int k) const { return active_host ? active_host[k] : k; }
   // Entries of dims / dims_host.
   int dims_entries() const { return frames; }
+};
+
+//   stride: the frames lie `stride` bytes apart, in src and dst alike (the
+// residual kernel's counters number the same); frame b starts b * stride after
+// frame 0.  More than one frame needs a 16-byte aligned stride that holds a
+// whole frame.  Images never read each other's rows: the set only moves the
+// base pointers.
+struct ImageSet : ImageTables {
+  int64_t stride = 0;
   // One plain image: nothing here that only the temporal kernels read.
   bool single() const { return frames <= 1 && !has_table() && !has_dims(); }
 };
@@ -166,12 +172,12 @@ constexpr int kResidualBlockRows = 32;
 // at (row 0, data column 0).  dst / dst_pitch: one pitched destination;
 // dst_bytes: the size of what dst points into, which the guards hold every
 // frame's output against.
-//   frames / src_stride / dst_stride: `frames` source frames src_stride bytes
-// apart go to destination frames dst_stride apart, all in one launch.
-//   dims / dims_host: optional table of `frames` SOURCE extents in the sense of
-// ImageSet::dims (the geometry above is then the envelope, g_row0 = 0); image
-// b's output extent is the ceil of its own extent, derived in the kernel.
-//   active / active_host: refused by name — a decimation covers every frame.
+//   images / src_stride / dst_stride: the frames (ImageTables above), source
+// frames src_stride bytes apart going to destination frames dst_stride apart,
+// all in one launch.  images.dims holds SOURCE extents (the geometry above is
+// then the envelope, g_row0 = 0); image b's output extent is the ceil of its
+// own extent, derived in the kernel.  An active table is refused by name: a
+// decimation covers every frame.
 // The source base, pitch and stride must be multiples of the load width (4 for
 // 4- and 8-byte pixels, 2 for 2 and 6); a destination whose base, pitch and
 // stride are multiples of 4 gets dword stores, any other byte stores.
@@ -187,13 +193,9 @@ struct DecimateLaunch {
   int64_t dst_bytes = 0;
   int pixel_bytes = 1;
   int factor = 1;
-  int frames = 1;
+  ImageTables images;
   int64_t src_stride = 0;
   int64_t dst_stride = 0;
-  const ImageDims* dims = nullptr;
-  const ImageDims* dims_host = nullptr;
-  const int32_t* active = nullptr;
-  const int32_t* active_host = nullptr;
 };
 void launch_decimate(const DecimateLaunch& a, hipStream_t stream);
 // Output rows one workgroup of k_decimate covers (tests place heights around
@@ -214,12 +216,10 @@ constexpr int kDecimateBlockRows = 16;
 // writes them); any other overlap of dst with orig or blur is refused.
 //   depth: 8 | 16 (row_bytes a whole number of samples).  k: amount x 16, in
 // [1, 255].  threshold: in [0, max].
-//   frames / orig_stride / blur_stride / dst_stride: `frames` frames at those
-// strides (each >= a frame), all in one launch.
-//   dims / dims_host: optional table of `frames` extents in the sense of
-// ImageSet::dims (the geometry above is then the envelope; image b occupies
-// rows [0, height_b) and bytes [0, row_bytes_b) of its frames).
-//   active / active_host: refused by name — every frame is sharpened.
+//   images / orig_stride / blur_stride / dst_stride: the frames (ImageTables
+// above) at those strides (each >= a frame), all in one launch.  With
+// images.dims the geometry above is the envelope.  An active table is refused
+// by name: every frame is sharpened.
 // Every base, pitch and stride must be a multiple of 16 and every pitch
 // >= round_up(row_bytes, 16).
 // Every guard is named "launch_unsharp: ..."; a refused launch writes nothing.
@@ -235,14 +235,10 @@ struct UnsharpLaunch {
   int depth = 8;
   int k = 16;
   int threshold = 0;
-  int frames = 1;
+  ImageTables images;
   int64_t orig_stride = 0;
   int64_t blur_stride = 0;
   int64_t dst_stride = 0;
-  const ImageDims* dims = nullptr;
-  const ImageDims* dims_host = nullptr;
-  const int32_t* active = nullptr;
-  const int32_t* active_host = nullptr;
 };
 void launch_unsharp(const UnsharpLaunch& a, hipStream_t stream);
 // Rows one workgroup of k_unsharp covers (tests place heights around it).

@@ -26,13 +26,10 @@
 //
 // A workgroup is 64 lanes x 4 waves; each wave marches down kRowsPerWave
 // output rows, so a workgroup covers 256 output bytes x kDecimateBlockRows
-// rows.  The grid is flat and image-major (chunks of the row fastest, then the
-// block rows, then the images), so a workgroup never spans two images; its
-// image moves both base pointers by img * stride in 64 bits before anything
-// else.  With an extents table (ImageSet::dims' sense: SOURCE extents) the
-// image's own output extent is derived here as the ceil of its own size, and a
-// workgroup of the envelope's grid with no output in its image leaves before
-// its first load.
+// rows.  The grid is flat and image-major (image_block in image_grid.hpp).
+// With an extents table (SOURCE extents) the image's own output extent is
+// derived here as the ceil of its own size, and a workgroup of the envelope's
+// grid with no output in its image leaves before its first load.
 //
 // Nothing outside [0, out_row_bytes) of rows [0, out_h) of a destination frame
 // is written and nothing outside [0, row_bytes) of the image's rows is read:
@@ -43,6 +40,8 @@
 
 #include "pconv/device.hpp"
 #include "pconv/kernels.hpp"
+#include "image_grid.hpp"
+#include "image_set.hpp"
 
 namespace pconv {
 namespace {
@@ -69,21 +68,15 @@ __global__ __launch_bounds__(256) void k_decimate(const uint8_t* __restrict__ sr
                                                   int factor, int blocks_x, int blocks_per_image, int64_t src_stride,
                                                   int64_t dst_stride, const ImageDims* __restrict__ dims) {
   constexpr int U = LoadUnit<PB>::value;
-  // Image of the batch: from the workgroup id (scalar); it only moves the two
-  // base pointers, in 64 bits, before anything else.
-  const unsigned img = blockIdx.x / static_cast<unsigned>(blocks_per_image);
-  const unsigned blk = blockIdx.x - img * static_cast<unsigned>(blocks_per_image);
+  const auto [img, bx, by] = image_block(blocks_x, blocks_per_image);
   src += static_cast<int64_t>(img) * src_stride;
   dst += static_cast<int64_t>(img) * dst_stride;
-  const int bx = static_cast<int>(blk % static_cast<unsigned>(blocks_x));
-  const int by = static_cast<int>(blk / static_cast<unsigned>(blocks_x));
   // Mixed sizes: the image's own extent replaces the envelope's (one scalar
-  // load; the min keeps a wrong table inside the frame; whole images, so
-  // first = 0).
+  // load; whole images, so first = 0).
   if (dims != nullptr) {
-    const ImageDims d = dims[img];
-    row_bytes = min(max(d.row_bytes, 0), row_bytes);
-    rows = min(max(d.height, 0), rows);
+    const ImageDims d = clamp_extent(dims[img], row_bytes, rows);
+    row_bytes = d.row_bytes;
+    rows = d.height;
   }
   // Output extent: the ceil of the image's own extent (in pixels, in rows).
   const int out_rb = ((row_bytes / PB + factor - 1) / factor) * PB;
@@ -124,15 +117,18 @@ __global__ __launch_bounds__(256) void k_decimate(const uint8_t* __restrict__ sr
 
 template <int PB>
 void launch_pb(const DecimateLaunch& a, int first, int64_t bx, int64_t by, bool aligned, hipStream_t s) {
-  const dim3 grid(static_cast<unsigned>(bx * by * a.frames)), block(64, 4);
+  const int frames = a.images.frames;
+  const dim3 grid(static_cast<unsigned>(bx * by * frames)), block(64, 4);
   const int rb = static_cast<int>(a.row_bytes), rows = static_cast<int>(a.rows);
-  const int64_t ss = a.frames > 1 ? a.src_stride : 0, ds = a.frames > 1 ? a.dst_stride : 0;
+  const int64_t ss = frames > 1 ? a.src_stride : 0, ds = frames > 1 ? a.dst_stride : 0;
   if (aligned)
     k_decimate<PB, true><<<grid, block, 0, s>>>(a.src, a.src_pitch, rb, rows, first, a.dst, a.dst_pitch, a.factor,
-                                                static_cast<int>(bx), static_cast<int>(bx * by), ss, ds, a.dims);
+                                                static_cast<int>(bx), static_cast<int>(bx * by), ss, ds,
+                                                a.images.dims);
   else
     k_decimate<PB, false><<<grid, block, 0, s>>>(a.src, a.src_pitch, rb, rows, first, a.dst, a.dst_pitch, a.factor,
-                                                 static_cast<int>(bx), static_cast<int>(bx * by), ss, ds, a.dims);
+                                                 static_cast<int>(bx), static_cast<int>(bx * by), ss, ds,
+                                                 a.images.dims);
 }
 
 }  // namespace
@@ -145,10 +141,10 @@ void launch_decimate(const DecimateLaunch& a, hipStream_t stream) {
   const int pb = a.pixel_bytes;
   PCONV_CHECK(pb == 1 || pb == 2 || pb == 3 || pb == 4 || pb == 6 || pb == 8,
               who + ": pixel_bytes " + num(pb) + " is none of 1, 2, 3, 4, 6, 8");
-  PCONV_CHECK(a.active == nullptr && a.active_host == nullptr,
-              who + ": an active table is not supported (every frame of the set is decimated)");
+  check_no_active(who, a.images, "decimated");
   PCONV_CHECK(a.src != nullptr && a.dst != nullptr, who + ": null frame pointer");
-  PCONV_CHECK(a.frames >= 1, who + ": frames must be >= 1");
+  const int frames = a.images.frames;
+  PCONV_CHECK(frames >= 1, who + ": frames must be >= 1");
   PCONV_CHECK(a.rows >= 1 && a.row_bytes >= pb, who + ": empty source frame");
   PCONV_CHECK(a.row_bytes % pb == 0, who + ": row bytes " + num(a.row_bytes) + " are no whole pixels of " + num(pb) +
                                          " bytes");
@@ -160,22 +156,10 @@ void launch_decimate(const DecimateLaunch& a, hipStream_t stream) {
   // The loads' width: a dword for PB 4 / 8, a ushort for PB 2 / 6.
   const int unit = pb % 4 == 0 ? 4 : pb % 2 == 0 ? 2 : 1;
   PCONV_CHECK(reinterpret_cast<uintptr_t>(a.src) % unit == 0 && a.src_pitch % unit == 0 &&
-                  (a.frames <= 1 || a.src_stride % unit == 0),
+                  (frames <= 1 || a.src_stride % unit == 0),
               who + ": source base, pitch and stride must be multiples of " + num(unit) + " for " + num(pb) +
                   "-byte pixels");
-  PCONV_CHECK((a.dims == nullptr) == (a.dims_host == nullptr),
-              who + ": dims and dims_host must be given together (the device table and its host copy)");
-  if (a.dims) {
-    PCONV_CHECK(a.g_row0 == 0, who + ": dims needs whole images (g_row0 = 0)");
-    for (int b = 0; b < a.frames; ++b) {
-      const ImageDims& d = a.dims_host[b];
-      PCONV_CHECK(d.row_bytes >= pb && d.row_bytes <= a.row_bytes && d.row_bytes % pb == 0,
-                  who + ": dims[" + num(b) + "].row_bytes " + num(d.row_bytes) +
-                      " is no whole number of pixels inside the envelope's " + num(a.row_bytes));
-      PCONV_CHECK(d.height >= 1 && d.height <= a.rows, who + ": dims[" + num(b) + "].height " + num(d.height) +
-                                                           " is outside [1, the envelope's " + num(a.rows) + "]");
-    }
-  }
+  check_extents(who, a.images, a.row_bytes, a.rows, pb, "pixels", a.g_row0 == 0, "g_row0 = 0");
   // Frame row r is kept when (g_row0 + r) % factor == 0: the first such row,
   // and the envelope's output extent (every image's own lies inside it).
   const int64_t first = (a.factor - a.g_row0 % a.factor) % a.factor;
@@ -184,25 +168,21 @@ void launch_decimate(const DecimateLaunch& a, hipStream_t stream) {
   PCONV_CHECK(a.dst_pitch >= out_rb, who + ": destination pitch " + num(a.dst_pitch) +
                                          " is smaller than an output row (" + num(out_rb) + " bytes)");
   const int64_t frame_extent = out_h > 0 ? (out_h - 1) * a.dst_pitch + out_rb : 0;
-  if (a.frames > 1) {
-    PCONV_CHECK(a.src_stride >= (a.rows - 1) * a.src_pitch + a.row_bytes,
-                who + ": src_stride " + num(a.src_stride) + " is smaller than a source frame: frames would overlap");
-    PCONV_CHECK(a.dst_stride >= frame_extent, who + ": dst_stride " + num(a.dst_stride) +
-                                                  " is smaller than an output frame (" + num(frame_extent) +
-                                                  " bytes): frames would overlap");
-    PCONV_CHECK(a.frames * a.dst_stride <= a.dst_bytes,
-                who + ": " + num(a.frames) + " frames at dst_stride " + num(a.dst_stride) + " exceed dst_bytes " +
+  if (frames > 1) {
+    check_frames_apart(who, "src_stride", a.src_stride, "a source frame", (a.rows - 1) * a.src_pitch + a.row_bytes);
+    check_frames_apart(who, "dst_stride", a.dst_stride, "an output frame", frame_extent);
+    PCONV_CHECK(frames * a.dst_stride <= a.dst_bytes,
+                who + ": " + num(frames) + " frames at dst_stride " + num(a.dst_stride) + " exceed dst_bytes " +
                     num(a.dst_bytes));
   }
-  PCONV_CHECK((a.frames - 1) * (a.frames > 1 ? a.dst_stride : 0) + frame_extent <= a.dst_bytes,
+  PCONV_CHECK((frames - 1) * (frames > 1 ? a.dst_stride : 0) + frame_extent <= a.dst_bytes,
               who + ": the output (" + num(out_h) + " rows of " + num(out_rb) + " bytes at pitch " +
                   num(a.dst_pitch) + ") exceeds dst_bytes " + num(a.dst_bytes));
   if (out_h == 0) return;  // a band without a selected row
   const int64_t bx = ceil_div<int64_t>(out_rb, kBlockBytes), by = ceil_div<int64_t>(out_h, kDecimateBlockRows);
-  PCONV_CHECK(bx * by < (int64_t(1) << 31) && bx * by * a.frames < (int64_t(1) << 31),
-              who + ": too many workgroups for one grid (images x blocks per image)");
+  check_flat_grid(who, bx, by, frames);
   const bool aligned = reinterpret_cast<uintptr_t>(a.dst) % 4 == 0 && a.dst_pitch % 4 == 0 &&
-                       (a.frames <= 1 || a.dst_stride % 4 == 0);
+                       (frames <= 1 || a.dst_stride % 4 == 0);
   const int f = static_cast<int>(first);
   switch (pb) {
     case 1: launch_pb<1>(a, f, bx, by, aligned, stream); break;

@@ -1,6 +1,8 @@
-// Host side of StencilLaunch::images (ImageSet, pconv/kernels.hpp), shared by
-// the kernel translation units: the launch guards, the four kernel arguments
-// every batch-capable kernel takes, and the tuners' live-workgroup count.
+// Host side of a launch's images (ImageTables and ImageSet, pconv/kernels.hpp),
+// shared by the kernel translation units: the launch guards, the four kernel
+// arguments every batch-capable temporal kernel takes, and the tuners'
+// live-workgroup count.  No HIP call and no device code: the guards also run
+// stand-alone (tests/cpp/test_ragged_native.cpp).
 #pragma once
 
 #include <algorithm>
@@ -14,6 +16,14 @@
 
 namespace pconv {
 
+// Frames `stride` bytes apart (`name`: the stride's field) do not overlap: the
+// stride holds `frame` ("a frame", "an output frame"), `frame_bytes` bytes.
+inline void check_frames_apart(const std::string& who, const char* name, int64_t stride, const char* frame,
+                               int64_t frame_bytes) {
+  PCONV_CHECK(stride >= frame_bytes, who + ": " + name + " " + std::to_string(stride) + " is smaller than " + frame +
+                                         " (" + std::to_string(frame_bytes) + " bytes): frames would overlap");
+}
+
 // At least one image in the grid, and frames that do not overlap: more than
 // one frame lies at a 16-byte aligned stride that holds a whole frame —
 // whatever the number of images an active-image table leaves in the grid.
@@ -22,9 +32,7 @@ inline void check_batch(const std::string& who, const StencilLaunch& a) {
   PCONV_CHECK(s.images() >= 1, who + ": batch must be >= 1");
   if (s.frames <= 1) return;
   PCONV_CHECK(s.stride % 16 == 0, who + ": batch_stride must be a multiple of 16");
-  PCONV_CHECK(s.stride >= (a.frame_hi - a.frame_lo) * a.pitch,
-              who + ": batch_stride " + std::to_string(s.stride) + " is smaller than a frame (" +
-                  std::to_string((a.frame_hi - a.frame_lo) * a.pitch) + " bytes): frames would overlap");
+  check_frames_apart(who, "batch_stride", s.stride, "a frame", (a.frame_hi - a.frame_lo) * a.pitch);
 }
 
 // The active-image table comes with its host copy and holds `count` strictly
@@ -48,25 +56,45 @@ inline void check_active(const std::string& who, const StencilLaunch& a) {
   }
 }
 
-// The extents table comes with its host copy, the launch covers whole images,
-// and every frame's image — named by an active-image table or not — is whole
-// pixels inside the envelope.  `ch`: bytes per pixel.
-inline void check_dims(const std::string& who, const StencilLaunch& a, int ch) {
-  const ImageSet& s = a.images;
+// A launch that covers every frame takes no active-image table; `verb`: what
+// it does to each ("decimated", "sharpened").
+inline void check_no_active(const std::string& who, const ImageTables& s, const char* verb) {
+  PCONV_CHECK(!s.has_table(),
+              who + ": an active table is not supported (every frame of the set is " + verb + ")");
+}
+
+// The extents table comes with its host copy, the launch covers whole images
+// (`whole`; `whole_rule` names what that asks of this launch), and every
+// frame's image — named by an active-image table or not — is a whole number
+// of `unit`-byte `noun` ("pixels", "samples") inside the envelope of
+// row_bytes x rows.
+inline void check_extents(const std::string& who, const ImageTables& s, int64_t row_bytes, int64_t rows, int unit,
+                          const char* noun, bool whole = true, const char* whole_rule = "") {
   PCONV_CHECK((s.dims == nullptr) == (s.dims_host == nullptr),
               who + ": dims and dims_host must be given together (the device table and its host copy)");
   if (!s.dims) return;
-  PCONV_CHECK(a.g_row0 == 0 && a.r0 == 0 && a.r1 == a.height,
-              who + ": dims needs whole images (g_row0 = 0, r0 = 0, r1 = height)");
+  PCONV_CHECK(whole, who + ": dims needs whole images (" + whole_rule + ")");
   for (int b = 0; b < s.dims_entries(); ++b) {
     const ImageDims& d = s.dims_host[b];
-    PCONV_CHECK(d.row_bytes >= ch && d.row_bytes <= a.row_bytes && d.row_bytes % ch == 0,
+    PCONV_CHECK(d.row_bytes >= unit && d.row_bytes <= row_bytes && d.row_bytes % unit == 0,
                 who + ": dims[" + std::to_string(b) + "].row_bytes " + std::to_string(d.row_bytes) +
-                    " is no whole number of pixels inside the envelope's " + std::to_string(a.row_bytes));
-    PCONV_CHECK(d.height >= 1 && d.height <= a.height,
+                    " is no whole number of " + noun + " inside the envelope's " + std::to_string(row_bytes));
+    PCONV_CHECK(d.height >= 1 && d.height <= rows,
                 who + ": dims[" + std::to_string(b) + "].height " + std::to_string(d.height) +
-                    " is outside [1, the envelope's " + std::to_string(a.height) + "]");
+                    " is outside [1, the envelope's " + std::to_string(rows) + "]");
   }
+}
+
+// check_extents for a temporal or residual launch.  `ch`: bytes per pixel.
+inline void check_dims(const std::string& who, const StencilLaunch& a, int ch) {
+  check_extents(who, a.images, a.row_bytes, a.height, ch, "pixels", a.g_row0 == 0 && a.r0 == 0 && a.r1 == a.height,
+                "g_row0 = 0, r0 = 0, r1 = height");
+}
+
+// A flat, image-major grid of `images` x (bx x by) workgroups fits one launch.
+inline void check_flat_grid(const std::string& who, int64_t bx, int64_t by, int64_t images) {
+  PCONV_CHECK(bx * by < (int64_t(1) << 31) && bx * by * images < (int64_t(1) << 31),
+              who + ": too many workgroups for one grid (images x blocks per image)");
 }
 
 // All guards of a launch's image set, in the one order every entry point

@@ -14,12 +14,11 @@
 // (none when its count is zero) lands on the device counter.
 //
 // An image batch (StencilLaunch::images) is a run-time argument, as in the
-// temporal kernels: the flat grid is batch x blocks_per_image workgroups,
-// image-major, so a workgroup never spans two images.  Its image comes from
-// the workgroup id (scalar) and does two things only: it moves the frame
-// pointer by img * batch_stride (64-bit) before anything else, and it picks
-// the counter the workgroup's atomic add lands on, counter[img].  One image is
-// the same instantiations on the same grid, adding to counter[0].
+// temporal kernels: the grid is flat and image-major (image_block in
+// image_grid.hpp).  A workgroup's image does two things only: it moves the
+// frame pointer by img * batch_stride and it picks the counter the workgroup's
+// atomic add lands on, counter[img].  One image is the same instantiations on
+// the same grid, adding to counter[0].
 //
 // Borders are applied to the registers, not read from the frame: rows outside
 // the global image are zeros (Zero) or the image's first / last row
@@ -33,6 +32,7 @@
 
 #include "pconv/device.hpp"
 #include "pconv/kernels.hpp"
+#include "image_grid.hpp"
 #include "image_set.hpp"
 #include "nine_tap.hpp"
 #include "tuning.hpp"
@@ -110,27 +110,24 @@ __global__ __launch_bounds__(256) void k_residual(const uint8_t* __restrict__ sr
                                                   const ImageDims* __restrict__ dims,
                                                   const int32_t* __restrict__ active, unsigned last_frame) {
   __shared__ u32 part[4];
-  // Image of the batch: from the workgroup id (scalar); it only moves the
-  // frame pointer and picks the counter.  Active images: the grid's slot names
-  // its frame through the table (one scalar load; the unsigned min keeps a
-  // wrong table inside the batch_frames frames and counters); from there on
-  // img is a frame index.
-  unsigned img = blockIdx.x / static_cast<unsigned>(blocks_per_image);
-  const unsigned blk = blockIdx.x - img * static_cast<unsigned>(blocks_per_image);
+  // The image only moves the frame pointer and picks the counter.  Active
+  // images: the grid's slot names its frame through the table (one scalar
+  // load; the unsigned min keeps a wrong table inside the batch_frames frames
+  // and counters); from there on img is a frame index.
+  const ImageBlock wg = image_block(blocks_x, blocks_per_image);
+  const int bx = wg.bx, by = wg.by;
+  unsigned img = wg.img;
   if (active != nullptr) img = min(static_cast<unsigned>(active[img]), last_frame);
   src += static_cast<int64_t>(img) * batch_stride;
-  const int bx = static_cast<int>(blk % static_cast<unsigned>(blocks_x));
-  const int by = static_cast<int>(blk / static_cast<unsigned>(blocks_x));
   // Mixed sizes: the image's own extent replaces the envelope's (one scalar
-  // load; img is workgroup-uniform; whole images, so r0 = img_lo = 0).  The
-  // min keeps a wrong table inside the frame.  A workgroup of the envelope's
-  // grid with no byte of this image adds nothing: gone before its first load
-  // and the barrier, no atomic.
+  // load; img is workgroup-uniform; whole images, so r0 = img_lo = 0 and
+  // img_hi = r1).  A workgroup of the envelope's grid with no byte of this
+  // image adds nothing: gone before its first load and the barrier, no atomic.
   if (dims != nullptr) {
-    const ImageDims d = dims[img];
-    row_bytes = min(d.row_bytes, row_bytes);
+    const ImageDims d = clamp_extent(dims[img], row_bytes, r1);
+    row_bytes = d.row_bytes;
     img_hi = min(d.height, img_hi);
-    r1 = min(d.height, r1);
+    r1 = d.height;
     if (bx * 1024 >= row_bytes || r0 + by * 4 * kRpt >= r1) return;
   }
   const int x = (bx * 64 + static_cast<int>(threadIdx.x)) * 16;
@@ -173,8 +170,7 @@ void launch_ch(const Filter& f, const StencilLaunch& a, uint64_t* counter, hipSt
   const int64_t bx = ceil_div<int64_t>(ceil_div<int64_t>(a.row_bytes, 16), 64);
   const int64_t by = ceil_div<int64_t>(rows, kResidualBlockRows);
   const int images = a.images.images();
-  PCONV_CHECK(bx * by < (int64_t(1) << 31) && bx * by * images < (int64_t(1) << 31),
-              "launch_residual: too many workgroups for one grid (batch x blocks per image)");
+  check_flat_grid("launch_residual", bx, by, images);
   const Taps9 tp = make_taps9(f);
   const dim3 grid(static_cast<unsigned>(bx * by * images)), block(64, 4);
   auto* ctr = reinterpret_cast<unsigned long long*>(counter);

@@ -20,12 +20,9 @@
 // original, one of the blurred frame, one 16-byte store.  A workgroup is 64
 // lanes x 4 waves and covers 1024 row bytes x kUnsharpBlockRows rows; each
 // wave marches down kRowsPerWave rows, all of whose loads are issued before the
-// first store.  The grid is flat and image-major (chunks of the row fastest,
-// then the block rows, then the images), so a workgroup never spans two
-// images; its image moves the three base pointers by img * stride in 64 bits
-// before anything else.  With an extents table (ImageSet::dims' sense) the
-// image's own extent, clamped to the envelope, replaces the envelope's, and a
-// workgroup with no byte of its image leaves before its first load.
+// first store.  The grid is flat and image-major (image_block in
+// image_grid.hpp); with an extents table a workgroup with no byte of its image
+// leaves before its first load.
 //
 // The lane that holds the row's end loads its 16 bytes like every other (the
 // guards keep round_up(row_bytes, 16) inside every pitch) and stores only the
@@ -42,6 +39,8 @@
 
 #include "pconv/device.hpp"
 #include "pconv/kernels.hpp"
+#include "image_grid.hpp"
+#include "image_set.hpp"
 
 namespace pconv {
 namespace {
@@ -75,21 +74,15 @@ __global__ __launch_bounds__(256) void k_unsharp(const uint8_t* __restrict__ ori
                                                  int blocks_x, int blocks_per_image, int64_t orig_stride,
                                                  int64_t blur_stride, int64_t dst_stride,
                                                  const ImageDims* __restrict__ dims) {
-  // Image of the batch: from the workgroup id (scalar); it only moves the three
-  // base pointers, in 64 bits, before anything else.
-  const unsigned img = blockIdx.x / static_cast<unsigned>(blocks_per_image);
-  const unsigned blk = blockIdx.x - img * static_cast<unsigned>(blocks_per_image);
+  const auto [img, bx, by] = image_block(blocks_x, blocks_per_image);
   orig += static_cast<int64_t>(img) * orig_stride;
   blur += static_cast<int64_t>(img) * blur_stride;
   dst += static_cast<int64_t>(img) * dst_stride;
-  const int bx = static_cast<int>(blk % static_cast<unsigned>(blocks_x));
-  const int by = static_cast<int>(blk / static_cast<unsigned>(blocks_x));
-  // Mixed sizes: the image's own extent replaces the envelope's (one scalar
-  // load; the min keeps a wrong table inside the frame).
+  // Mixed sizes: the image's own extent replaces the envelope's (one scalar load).
   if (dims != nullptr) {
-    const ImageDims d = dims[img];
-    row_bytes = min(max(d.row_bytes, 0), row_bytes);
-    rows = min(max(d.height, 0), rows);
+    const ImageDims d = clamp_extent(dims[img], row_bytes, rows);
+    row_bytes = d.row_bytes;
+    rows = d.height;
   }
   if (bx * kBlockBytes >= row_bytes || by * kUnsharpBlockRows >= rows) return;  // before the first load
 
@@ -140,16 +133,16 @@ void launch_unsharp(const UnsharpLaunch& a, hipStream_t stream) {
   PCONV_CHECK(a.k >= 1 && a.k <= 255, who + ": k " + num(a.k) + " is outside [1, 255] (amount x 16)");
   PCONV_CHECK(a.threshold >= 0 && a.threshold <= mx,
               who + ": threshold " + num(a.threshold) + " is outside [0, " + num(mx) + "]");
-  PCONV_CHECK(a.active == nullptr && a.active_host == nullptr,
-              who + ": an active table is not supported (every frame of the set is sharpened)");
+  check_no_active(who, a.images, "sharpened");
   PCONV_CHECK(a.orig != nullptr && a.blur != nullptr && a.dst != nullptr, who + ": null frame pointer");
-  PCONV_CHECK(a.frames >= 1, who + ": frames must be >= 1");
+  const int frames = a.images.frames;
+  PCONV_CHECK(frames >= 1, who + ": frames must be >= 1");
   PCONV_CHECK(a.rows >= 1 && a.row_bytes >= sb, who + ": empty frame");
   PCONV_CHECK(a.row_bytes % sb == 0,
               who + ": row bytes " + num(a.row_bytes) + " are no whole samples of " + num(sb) + " bytes");
   PCONV_CHECK(a.row_bytes < (int64_t(1) << 31) - kBlockBytes && a.rows < (int64_t(1) << 31) - 64,
               who + ": geometry exceeds 32-bit kernel indices");
-  const bool many = a.frames > 1;
+  const bool many = frames > 1;
   PCONV_CHECK(addr(a.orig) % 16 == 0 && addr(a.blur) % 16 == 0 && addr(a.dst) % 16 == 0 && a.orig_pitch % 16 == 0 &&
                   a.blur_pitch % 16 == 0 && a.dst_pitch % 16 == 0 &&
                   (!many || (a.orig_stride % 16 == 0 && a.blur_stride % 16 == 0 && a.dst_stride % 16 == 0)),
@@ -159,29 +152,18 @@ void launch_unsharp(const UnsharpLaunch& a, hipStream_t stream) {
   PCONV_CHECK(a.orig_pitch >= reach && a.blur_pitch >= reach && a.dst_pitch >= reach,
               who + ": a pitch is smaller than the row bytes rounded up to 16 (" + num(reach) + ")");
   const auto frame_bytes = [&](int64_t pitch) { return (a.rows - 1) * pitch + reach; };
-  if (many)
-    PCONV_CHECK(a.orig_stride >= frame_bytes(a.orig_pitch) && a.blur_stride >= frame_bytes(a.blur_pitch) &&
-                    a.dst_stride >= frame_bytes(a.dst_pitch),
-                who + ": a stride is smaller than its frame: frames would overlap");
-  PCONV_CHECK((a.dims == nullptr) == (a.dims_host == nullptr),
-              who + ": dims and dims_host must be given together (the device table and its host copy)");
-  if (a.dims) {
-    for (int b = 0; b < a.frames; ++b) {
-      const ImageDims& d = a.dims_host[b];
-      PCONV_CHECK(d.row_bytes >= sb && d.row_bytes <= a.row_bytes && d.row_bytes % sb == 0,
-                  who + ": dims[" + num(b) + "].row_bytes " + num(d.row_bytes) +
-                      " is no whole number of samples inside the envelope's " + num(a.row_bytes));
-      PCONV_CHECK(d.height >= 1 && d.height <= a.rows, who + ": dims[" + num(b) + "].height " + num(d.height) +
-                                                           " is outside [1, the envelope's " + num(a.rows) + "]");
-    }
+  if (many) {
+    check_frames_apart(who, "orig_stride", a.orig_stride, "a frame", frame_bytes(a.orig_pitch));
+    check_frames_apart(who, "blur_stride", a.blur_stride, "a frame", frame_bytes(a.blur_pitch));
+    check_frames_apart(who, "dst_stride", a.dst_stride, "a frame", frame_bytes(a.dst_pitch));
   }
+  check_extents(who, a.images, a.row_bytes, a.rows, sb, "samples");
   const int64_t bx = ceil_div<int64_t>(a.row_bytes, kBlockBytes), by = ceil_div<int64_t>(a.rows, kUnsharpBlockRows);
-  PCONV_CHECK(bx * by < (int64_t(1) << 31) && bx * by * a.frames < (int64_t(1) << 31),
-              who + ": too many workgroups for one grid (images x blocks per image)");
+  check_flat_grid(who, bx, by, frames);
   // dst == blur at the same pitch and stride is in place; any other overlap of
   // the destination with a source is refused (byte ranges of all frames).
   const auto span = [&](int64_t pitch, int64_t stride) {
-    return static_cast<uintptr_t>((many ? (a.frames - 1) * stride : 0) + frame_bytes(pitch));
+    return static_cast<uintptr_t>((many ? (frames - 1) * stride : 0) + frame_bytes(pitch));
   };
   const auto overlap = [&](const uint8_t* p, uintptr_t pn, const uint8_t* q, uintptr_t qn) {
     return addr(p) < addr(q) + qn && addr(q) < addr(p) + pn;
@@ -191,17 +173,17 @@ void launch_unsharp(const UnsharpLaunch& a, hipStream_t stream) {
   PCONV_CHECK(in_place || !overlap(a.dst, dn, a.blur, span(a.blur_pitch, a.blur_stride)),
               who + ": dst overlaps blur (in place needs dst == blur with equal pitch and stride)");
   PCONV_CHECK(!overlap(a.dst, dn, a.orig, span(a.orig_pitch, a.orig_stride)), who + ": dst overlaps orig");
-  const dim3 grid(static_cast<unsigned>(bx * by * a.frames)), block(64, 4);
+  const dim3 grid(static_cast<unsigned>(bx * by * frames)), block(64, 4);
   const int rb = static_cast<int>(a.row_bytes), rows = static_cast<int>(a.rows);
   const int64_t os = many ? a.orig_stride : 0, bs = many ? a.blur_stride : 0, ds = many ? a.dst_stride : 0;
   if (a.depth == 8)
     k_unsharp<8><<<grid, block, 0, stream>>>(a.orig, a.orig_pitch, a.blur, a.blur_pitch, a.dst, a.dst_pitch, rb, rows,
                                              a.k, a.threshold, static_cast<int>(bx), static_cast<int>(bx * by), os, bs,
-                                             ds, a.dims);
+                                             ds, a.images.dims);
   else
     k_unsharp<16><<<grid, block, 0, stream>>>(a.orig, a.orig_pitch, a.blur, a.blur_pitch, a.dst, a.dst_pitch, rb, rows,
                                               a.k, a.threshold, static_cast<int>(bx), static_cast<int>(bx * by), os, bs,
-                                              ds, a.dims);
+                                              ds, a.images.dims);
   PCONV_HIP_CHECK(hipGetLastError());
 }
 

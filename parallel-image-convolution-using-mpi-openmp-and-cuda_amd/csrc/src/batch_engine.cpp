@@ -174,7 +174,7 @@ void BatchEngine::download_sized(uint8_t* p, bool device) {
 // frames of the decimated envelope, from which one pitched copy per image (the
 // copies of copy_images) moves the image regions.
 
-void BatchEngine::decimate_images(uint8_t* p, int n, int factor, const ImageDims* extents, bool device) {
+void BatchEngine::decimate_images(uint8_t* p, int n, int factor, bool device) {
   check_decimate(factor);
   if (n == 0) return;
   PCONV_CHECK(!stream_capturing(cs_), "BatchEngine: a decimated download is not captured into a hipGraph");
@@ -188,12 +188,9 @@ void BatchEngine::decimate_images(uint8_t* p, int n, int factor, const ImageDims
   d.rows = lay_.rows;
   d.pixel_bytes = static_cast<int>(pb);
   d.factor = factor;
-  d.frames = n;
+  d.images = image_tables(n);
   d.src_stride = stride_;
-  if (extents) {
-    d.dims = reinterpret_cast<const ImageDims*>(dims_.dev.data());
-    d.dims_host = extents;
-  }
+  const ImageDims* extents = d.images.dims_host;  // mixed mode: the packed images have a row pitch each
   if (device && !extents) {
     d.dst = p;
     d.dst_pitch = orb;
@@ -231,13 +228,13 @@ void BatchEngine::download_decimated(uint8_t* p, int n, int factor, bool device)
   PCONV_CHECK(sizes_.empty(), "BatchEngine::download_decimated: the upload was mixed-size (download_sized_decimated)");
   PCONV_CHECK(p != nullptr || n == 0, "BatchEngine::download_decimated: null destination");
   if (factor == 1) return download(p, n, device);
-  decimate_images(p, n, factor, nullptr, device);
+  decimate_images(p, n, factor, device);
 }
 
 void BatchEngine::download_sized_decimated(uint8_t* p, int factor, bool device) {
   PCONV_CHECK(p != nullptr || sizes_.empty(), "BatchEngine::download_sized_decimated: null destination");
   if (factor == 1) return download_sized(p, device);
-  decimate_images(p, static_cast<int>(dims_host_.size()), factor, dims_host_.data(), device);
+  decimate_images(p, static_cast<int>(dims_host_.size()), factor, device);
 }
 
 int64_t decimated_packed_bytes(const ImageGeom& env, const std::vector<ImageSize>& sizes, int factor) {
@@ -284,18 +281,30 @@ void BatchEngine::apply_unsharp(int k, int threshold, int n) {
   u.depth = geom_.depth;
   u.k = k;
   u.threshold = threshold;
-  u.frames = n;
+  u.images = image_tables(n);
   u.orig_stride = u.blur_stride = u.dst_stride = stride_;
-  if (!sizes_.empty()) {
-    u.dims = reinterpret_cast<const ImageDims*>(dims_.dev.data());
-    u.dims_host = dims_host_.data();
-  }
   launch_unsharp(u, cs_);
 }
 
-// What every launch over images [0, n) of the current frames shares: whole
-// images, the extents table in mixed mode, the table of open images while a
-// compacting run_until_stable has retired some.
+// Images [0, n) for a launch: the extents table in mixed mode, the table of
+// open images while a compacting run_until_stable has retired some.
+ImageTables BatchEngine::image_tables(int n) const {
+  ImageTables t;
+  t.frames = n;
+  if (!sizes_.empty()) {
+    t.dims = reinterpret_cast<const ImageDims*>(dims_.dev.data());
+    t.dims_host = dims_host_.data();
+  }
+  if (!active_host_.empty()) {
+    t.active = reinterpret_cast<const int32_t*>(active_.dev.data());
+    t.active_host = active_host_.data();
+    t.count = static_cast<int>(active_host_.size());
+  }
+  return t;
+}
+
+// What every temporal and residual launch over images [0, n) of the current
+// frames shares: whole images, their tables, the frames' stride.
 StencilLaunch BatchEngine::base_launch(int n) const {
   StencilLaunch a;
   a.src = frame_at(cur_);
@@ -309,17 +318,8 @@ StencilLaunch BatchEngine::base_launch(int n) const {
   a.height = geom_.height;
   a.border = opt_.border;
   a.depth = geom_.depth;
-  a.images.frames = n;
+  static_cast<ImageTables&>(a.images) = image_tables(n);
   a.images.stride = stride_;
-  if (!sizes_.empty()) {
-    a.images.dims = reinterpret_cast<const ImageDims*>(dims_.dev.data());
-    a.images.dims_host = dims_host_.data();
-  }
-  if (!active_host_.empty()) {
-    a.images.active = reinterpret_cast<const int32_t*>(active_.dev.data());
-    a.images.active_host = active_host_.data();
-    a.images.count = static_cast<int>(active_host_.size());
-  }
   return a;
 }
 

@@ -88,6 +88,24 @@ class PyHaloTransport : public HaloTransport {
   const char* name() const override { return "python"; }
 };
 
+// Diagnostics of the raw-pointer launch bindings: `timed` launches, each
+// between two timing events on stream `s`; synchronises the stream (also when
+// timed = 0) and returns the ms of each.
+template <class Launch>
+std::vector<double> time_launches(int timed, hipStream_t s, Launch&& launch) {
+  std::vector<Event> ev;
+  for (int i = 0; i < 2 * timed; ++i) ev.push_back(Event::create(true));
+  for (int i = 0; i < timed; ++i) {
+    ev[2 * i].record(s);
+    launch();
+    ev[2 * i + 1].record(s);
+  }
+  PCONV_HIP_CHECK(hipStreamSynchronize(s));
+  std::vector<double> ms;
+  for (int i = 0; i < timed; ++i) ms.push_back(Event::elapsed_ms(ev[2 * i], ev[2 * i + 1]));
+  return ms;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(_pconv_native, m) {
@@ -447,40 +465,49 @@ PYBIND11_MODULE(_pconv_native, m) {
                                {static_cast<py::ssize_t>(b.size())}, {1});
       });
 
-  // StencilLaunch::images from the launch bindings' keyword arguments; the
-  // vectors hold the tables' host copies for the duration of the call.
-  //   batch / batch_stride: the images of the grid and the bytes between
-  // frames.  active / active_ptr: the table of open images, as a list of
-  // `batch` frame indices (the host copy) and the device table's address; the
-  // frames at the stride then number `batch_frames`, without a table `batch`.
+  // A launch's images from the launch bindings' keyword arguments; the vectors
+  // hold the tables' host copies for the duration of the call.
   //   dims / dims_ptr: the extents as a list of one (row_bytes, height) pair per
-  // FRAME (the host copy) and the device table's address.
+  // FRAME (the host copy) and the device table's address.  active / active_ptr:
+  // the table of open images, as a list of frame indices and the device
+  // table's address.
+  //   batch / batch_stride (the ImageSet of launch_stencil and launch_residual*):
+  // the images of the grid and the bytes between frames; the active list holds
+  // `batch` indices, and the frames at the stride then number `batch_frames`,
+  // without a table `batch`.
   struct ImageSetArgs {
     std::vector<int32_t> active_host;
     std::vector<ImageDims> dims_host;
-    void fill(ImageSet& s, int batch, int64_t batch_stride, const py::object& dims, uintptr_t dims_ptr,
-              const py::object& active = py::none(), uintptr_t active_ptr = 0, int batch_frames = 1) {
-      const bool table = !active.is_none() || active_ptr != 0;
-      s.frames = table ? batch_frames : batch;
-      s.stride = batch_stride;
-      s.count = table ? batch : 0;
+    // The dims list must hold dims_n pairs (`dims_holds` says so), the active
+    // list active_n indices (below 0: any number, for the launches that refuse it).
+    void fill(ImageTables& s, int frames, const py::object& dims, uintptr_t dims_ptr, int64_t dims_n,
+              const char* dims_holds, const py::object& active, uintptr_t active_ptr, int64_t active_n = -1) {
+      s.frames = frames;
       if (!active.is_none()) {
         active_host = active.cast<std::vector<int32_t>>();
-        PCONV_CHECK(static_cast<int64_t>(active_host.size()) == batch,
+        PCONV_CHECK(active_n < 0 || static_cast<int64_t>(active_host.size()) == active_n,
                     "active: the list must hold `batch` frame indices");
         s.active_host = active_host.data();
+        s.count = static_cast<int>(active_host.size());
       }
       s.active = reinterpret_cast<const int32_t*>(active_ptr);
       if (!dims.is_none()) {
         for (const auto& d : dims.cast<std::vector<std::pair<int32_t, int32_t>>>())
           dims_host.push_back(ImageDims{d.first, d.second});
-        PCONV_CHECK(static_cast<int64_t>(dims_host.size()) == (s.active_host ? batch_frames : batch),
-                    s.active_host
-                        ? "dims: with an active table the list must hold `batch_frames` (row_bytes, height) pairs"
-                        : "dims: the list must hold `batch` (row_bytes, height) pairs");
+        PCONV_CHECK(static_cast<int64_t>(dims_host.size()) == dims_n,
+                    std::string("dims: ") + dims_holds + " (row_bytes, height) pairs");
         s.dims_host = dims_host.data();
       }
       s.dims = reinterpret_cast<const ImageDims*>(dims_ptr);
+    }
+    void fill(ImageSet& s, int batch, int64_t batch_stride, const py::object& dims, uintptr_t dims_ptr,
+              const py::object& active = py::none(), uintptr_t active_ptr = 0, int batch_frames = 1) {
+      const bool listed = !active.is_none(), table = listed || active_ptr != 0;
+      fill(static_cast<ImageTables&>(s), table ? batch_frames : batch, dims, dims_ptr, listed ? batch_frames : batch,
+           listed ? "with an active table the list must hold `batch_frames`" : "the list must hold `batch`", active,
+           active_ptr, batch);
+      s.stride = batch_stride;
+      s.count = table ? batch : 0;
     }
   };
   m.def(
@@ -603,39 +630,14 @@ PYBIND11_MODULE(_pconv_native, m) {
         a.dst_bytes = dst_bytes;
         a.pixel_bytes = pixel_bytes;
         a.factor = factor;
-        a.frames = frames;
         a.src_stride = src_stride;
         a.dst_stride = dst_stride;
-        std::vector<ImageDims> dims_host;
-        if (!dims.is_none()) {
-          for (const auto& d : dims.cast<std::vector<std::pair<int32_t, int32_t>>>())
-            dims_host.push_back(ImageDims{d.first, d.second});
-          PCONV_CHECK(static_cast<int64_t>(dims_host.size()) == frames,
-                      "dims: the list must hold `frames` (row_bytes, height) pairs");
-          a.dims_host = dims_host.data();
-        }
-        a.dims = reinterpret_cast<const ImageDims*>(dims_ptr);
-        std::vector<int32_t> active_host;
-        if (!active.is_none()) {
-          active_host = active.cast<std::vector<int32_t>>();
-          a.active_host = active_host.data();
-        }
-        a.active = reinterpret_cast<const int32_t*>(active_ptr);
+        ImageSetArgs images;
+        images.fill(a.images, frames, dims, dims_ptr, frames, "the list must hold `frames`", active, active_ptr);
         hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-        std::vector<double> ms;
         py::gil_scoped_release nogil;
         launch_decimate(a, s);
-        // diagnostics: `timed` more launches, each between two timing events on the stream
-        std::vector<Event> ev;
-        for (int i = 0; i < 2 * timed; ++i) ev.push_back(Event::create(true));
-        for (int i = 0; i < timed; ++i) {
-          ev[2 * i].record(s);
-          launch_decimate(a, s);
-          ev[2 * i + 1].record(s);
-        }
-        PCONV_HIP_CHECK(hipStreamSynchronize(s));
-        for (int i = 0; i < timed; ++i) ms.push_back(Event::elapsed_ms(ev[2 * i], ev[2 * i + 1]));
-        return ms;
+        return time_launches(timed, s, [&] { launch_decimate(a, s); });
       },
       py::arg("src"), py::arg("src_pitch"), py::arg("row_bytes"), py::arg("rows"), py::arg("dst"),
       py::arg("dst_pitch"), py::arg("dst_bytes"), py::arg("pixel_bytes"), py::arg("factor"), py::arg("g_row0") = 0,
@@ -665,40 +667,15 @@ PYBIND11_MODULE(_pconv_native, m) {
         a.depth = depth;
         a.k = k;
         a.threshold = threshold;
-        a.frames = frames;
         a.orig_stride = orig_stride;
         a.blur_stride = blur_stride;
         a.dst_stride = dst_stride;
-        std::vector<ImageDims> dims_host;
-        if (!dims.is_none()) {
-          for (const auto& d : dims.cast<std::vector<std::pair<int32_t, int32_t>>>())
-            dims_host.push_back(ImageDims{d.first, d.second});
-          PCONV_CHECK(static_cast<int64_t>(dims_host.size()) == frames,
-                      "dims: the list must hold `frames` (row_bytes, height) pairs");
-          a.dims_host = dims_host.data();
-        }
-        a.dims = reinterpret_cast<const ImageDims*>(dims_ptr);
-        std::vector<int32_t> active_host;
-        if (!active.is_none()) {
-          active_host = active.cast<std::vector<int32_t>>();
-          a.active_host = active_host.data();
-        }
-        a.active = reinterpret_cast<const int32_t*>(active_ptr);
+        ImageSetArgs images;
+        images.fill(a.images, frames, dims, dims_ptr, frames, "the list must hold `frames`", active, active_ptr);
         hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-        std::vector<double> ms;
         py::gil_scoped_release nogil;
         launch_unsharp(a, s);
-        // diagnostics: `timed` more launches, each between two timing events on the stream
-        std::vector<Event> ev;
-        for (int i = 0; i < 2 * timed; ++i) ev.push_back(Event::create(true));
-        for (int i = 0; i < timed; ++i) {
-          ev[2 * i].record(s);
-          launch_unsharp(a, s);
-          ev[2 * i + 1].record(s);
-        }
-        PCONV_HIP_CHECK(hipStreamSynchronize(s));
-        for (int i = 0; i < timed; ++i) ms.push_back(Event::elapsed_ms(ev[2 * i], ev[2 * i + 1]));
-        return ms;
+        return time_launches(timed, s, [&] { launch_unsharp(a, s); });
       },
       py::arg("orig"), py::arg("orig_pitch"), py::arg("blur"), py::arg("blur_pitch"), py::arg("dst"),
       py::arg("dst_pitch"), py::arg("row_bytes"), py::arg("rows"), py::arg("depth") = 8, py::arg("k") = 16,
@@ -716,18 +693,8 @@ PYBIND11_MODULE(_pconv_native, m) {
         const uint8_t* s = reinterpret_cast<const uint8_t*>(src);
         uint8_t* d = reinterpret_cast<uint8_t*>(dst);
         py::gil_scoped_release nogil;
-        std::vector<Event> ev;
-        for (int i = 0; i < 2 * timed; ++i) ev.push_back(Event::create(true));
         launch_copy_rows(s, sp, d, dp, row_bytes, rows, nullptr);
-        for (int i = 0; i < timed; ++i) {
-          ev[2 * i].record(nullptr);
-          launch_copy_rows(s, sp, d, dp, row_bytes, rows, nullptr);
-          ev[2 * i + 1].record(nullptr);
-        }
-        PCONV_HIP_CHECK(hipStreamSynchronize(nullptr));
-        std::vector<double> ms;
-        for (int i = 0; i < timed; ++i) ms.push_back(Event::elapsed_ms(ev[2 * i], ev[2 * i + 1]));
-        return ms;
+        return time_launches(timed, nullptr, [&] { launch_copy_rows(s, sp, d, dp, row_bytes, rows, nullptr); });
       },
       py::arg("src"), py::arg("src_pitch"), py::arg("dst"), py::arg("dst_pitch"), py::arg("row_bytes"),
       py::arg("rows"), py::arg("timed") = 0,

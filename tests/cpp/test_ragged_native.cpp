@@ -1,6 +1,7 @@
 // Native unit tests for the host side of a launch's image set (no GPU, no HIP
 // calls): the extents table BatchEngine::upload_sized builds, the packed
 // buffer's size, the launch guards of StencilLaunch::images and their order,
+// the guards they share with launch_decimate and launch_unsharp (ImageTables),
 // the kernels' image-set arguments and the tuners' live-workgroup count.  Built by `make -C <pkg>/csrc test-native` with
 // AddressSanitizer + UndefinedBehaviorSanitizer next to test_native.cpp.
 #include <cstdio>
@@ -192,6 +193,93 @@ void test_guard_order() {
   EXPECT(thrown([&] { check_temporal_only("t", "int9", {{"active", false}, {"dims", false}}); }).empty());
 }
 
+// The shared guards as launch_decimate and launch_unsharp call them: on bare
+// ImageTables, with the launch's own envelope, unit and noun.
+void test_pointwise_guards() {
+  static const ImageDims device_dims[4] = {};  // only the addresses are looked at
+  static const int32_t device_active[4] = {};
+  const std::vector<ImageDims> good = {{240, 10}, {6, 1}, {12, 10}};
+  ImageTables t;
+  t.frames = 3;
+  EXPECT(thrown([&] { check_extents("t", t, 240, 10, 6, "pixels"); }).empty());  // no table: nothing to check
+  EXPECT(!t.has_dims() && !t.has_table() && t.images() == 3 && t.dims_entries() == 3);
+  t.dims_host = good.data();
+  EXPECT(has(thrown([&] { check_extents("t", t, 240, 10, 6, "pixels"); }),
+             "t: dims and dims_host must be given together (the device table and its host copy)"));
+  t.dims_host = nullptr;
+  t.dims = device_dims;
+  EXPECT(has(thrown([&] { check_extents("t", t, 240, 10, 2, "samples"); }), "t: dims and dims_host must be given together"));
+  t.dims_host = good.data();
+  EXPECT(thrown([&] { check_extents("t", t, 240, 10, 6, "pixels"); }).empty());
+  EXPECT(thrown([&] { check_extents("t", t, 240, 10, 2, "samples"); }).empty());
+  // whole images, in the words of the launch that asks (launch_decimate: g_row0 = 0), after the pair, before the entries
+  EXPECT(has(thrown([&] { check_extents("t", t, 240, 10, 6, "pixels", false, "g_row0 = 0"); }),
+             "t: dims needs whole images (g_row0 = 0)"));
+  const auto with_entry = [&](int at, ImageDims d) {
+    std::vector<ImageDims> v = good;
+    v[at] = d;
+    return v;
+  };
+  // unit 2, "samples" (launch_unsharp at depth 16): odd, none, beyond the envelope, negative
+  for (const int rb : {5, 0, 1, 242, -2}) {
+    const std::vector<ImageDims> bad = with_entry(1, {rb, 1});
+    t.dims_host = bad.data();
+    EXPECT(has(thrown([&] { check_extents("t", t, 240, 10, 2, "samples"); }),
+               ("t: dims[1].row_bytes " + std::to_string(rb) + " is no whole number of samples inside the envelope's 240")
+                   .c_str()));
+  }
+  // unit 6, "pixels" (launch_decimate, 16-bit rgb): half a pixel, a whole sample but no pixel, beyond the envelope
+  for (const int rb : {3, 8, 0, 246}) {
+    const std::vector<ImageDims> bad = with_entry(2, {rb, 1});
+    t.dims_host = bad.data();
+    EXPECT(has(thrown([&] { check_extents("t", t, 240, 10, 6, "pixels"); }),
+               ("t: dims[2].row_bytes " + std::to_string(rb) + " is no whole number of pixels inside the envelope's 240")
+                   .c_str()));
+  }
+  const std::vector<ImageDims> four_samples = with_entry(2, {8, 1});  // no 6-byte pixels, but whole 2-byte samples
+  t.dims_host = four_samples.data();
+  EXPECT(thrown([&] { check_extents("t", t, 240, 10, 2, "samples"); }).empty());
+  for (const int h : {0, 11, -1}) {
+    const std::vector<ImageDims> bad = with_entry(0, {240, h});
+    t.dims_host = bad.data();
+    EXPECT(has(thrown([&] { check_extents("t", t, 240, 10, 6, "pixels"); }),
+               ("t: dims[0].height " + std::to_string(h) + " is outside [1, the envelope's 10]").c_str()));
+  }
+  // the first bad entry is the one reported, its row bytes before its height
+  const std::vector<ImageDims> two = {{240, 10}, {7, 0}, {0, 0}};
+  t.dims_host = two.data();
+  EXPECT(has(thrown([&] { check_extents("t", t, 240, 10, 6, "pixels"); }), "dims[1].row_bytes 7"));
+
+  // an active table, by either pointer
+  ImageTables a;
+  a.frames = 2;
+  EXPECT(thrown([&] { check_no_active("t", a, "decimated"); }).empty());
+  const std::vector<int32_t> table = {0, 1};
+  a.active_host = table.data();
+  EXPECT(has(thrown([&] { check_no_active("t", a, "decimated"); }),
+             "t: an active table is not supported (every frame of the set is decimated)"));
+  a.active_host = nullptr;
+  a.active = device_active;
+  EXPECT(has(thrown([&] { check_no_active("t", a, "sharpened"); }),
+             "t: an active table is not supported (every frame of the set is sharpened)"));
+
+  // the flat grid: blocks per image and images x blocks per image both below 2^31
+  EXPECT(thrown([&] { check_flat_grid("t", 64, 64, (int64_t(1) << 19) - 1); }).empty());
+  EXPECT(thrown([&] { check_flat_grid("t", 1, (int64_t(1) << 31) - 1, 1); }).empty());
+  EXPECT(has(thrown([&] { check_flat_grid("t", 1, int64_t(1) << 12, int64_t(1) << 20); }),
+             "t: too many workgroups for one grid"));
+  EXPECT(has(thrown([&] { check_flat_grid("t", int64_t(1) << 16, int64_t(1) << 15, 1); }),
+             "t: too many workgroups for one grid"));
+
+  // frames at least a frame apart
+  const int64_t frame = 9 * 384 + 240;
+  EXPECT(thrown([&] { check_frames_apart("t", "dst_stride", frame, "an output frame", frame); }).empty());
+  EXPECT(has(thrown([&] { check_frames_apart("t", "dst_stride", frame - 1, "an output frame", frame); }),
+             "t: dst_stride 3695 is smaller than an output frame (3696 bytes): frames would overlap"));
+  EXPECT(has(thrown([&] { check_frames_apart("t", "orig_stride", 0, "a frame", frame); }),
+             "t: orig_stride 0 is smaller than a frame (3696 bytes): frames would overlap"));
+}
+
 void test_batch_kernel_args() {
   StencilLaunch lone;  // stride 0 whatever the field holds: the kernels add nothing to the base pointers
   lone.images.stride = 4096;
@@ -241,6 +329,7 @@ int main() {
   test_guards();
   test_active_guards();
   test_guard_order();
+  test_pointwise_guards();
   test_batch_kernel_args();
   test_live_workgroups();
   std::printf("ragged native tests: %d checks, %d failures\n", g_checks, g_failures);

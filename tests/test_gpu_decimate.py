@@ -141,6 +141,44 @@ def test_raw_kernel_frames_and_dims(native, pb, store):
     _decimate_case(native, rng, pb, 2, w, h, store, frames=4, sizes=sizes)
 
 
+@pytest.mark.parametrize("s", [1, 5])
+def test_kernel_clamps_a_device_table_that_disagrees_with_its_host_copy(native, s):
+    """The guards read the host list; the kernel reads the device table and
+    clamps each entry to the envelope.  Entries beyond the envelope give
+    exactly the envelope's output, entries below zero leave the frame alone.
+    At both factors the 4 pixels and the one row more would each add to the
+    output; unclamped they are read from frame 0's pad and ghost row and land
+    in the destination's spare bytes and spare row, inside the buffers: a wrong
+    kernel fails the comparison."""
+    import torch
+
+    rng = np.random.default_rng(977 + s)
+    pb, w, h, frames = 4, 10, 5, 2
+    rb = w * pb
+    imgs, src, pitch, stride, src_off = _src_frames(rng, pb, w, h, frames)
+    assert rb + 16 <= pitch - 16
+    out_rb, out_h = _ceil(w, s) * pb, _ceil(h, s)
+    assert _ceil(w + 4, s) * pb > out_rb and _ceil(h + 1, s) > out_h
+    dst_pitch = _ceil(w + 4, s) * pb + 8
+    dst_stride = (_ceil(h + 1, s) + 1) * dst_pitch
+    dst = torch.full((frames * dst_stride + 2 * GUARD,), CANARY, dtype=torch.uint8, device="cuda")
+    expect = np.full((frames, dst_stride // dst_pitch, dst_pitch), CANARY, np.uint8)
+    expect[0, :out_h, :out_rb] = imgs[0].reshape(h, w, pb)[::s, ::s].reshape(out_h, out_rb)
+    table = torch.tensor([[rb + 16, h + 1], [-1, -1]], dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    native.launch_decimate(src.data_ptr() + src_off, pitch, rb, h, dst.data_ptr() + GUARD, dst_pitch,
+                           frames * dst_stride, pb, s, frames=frames, src_stride=stride, dst_stride=dst_stride,
+                           stream=torch.cuda.current_stream().cuda_stream, dims=[(rb, h), (rb, h)],
+                           dims_ptr=table.data_ptr())
+    torch.cuda.synchronize()
+    got = dst.cpu().numpy()
+    assert (got[:GUARD] == CANARY).all() and (got[-GUARD:] == CANARY).all(), "a canary outside the frames"
+    got = got[GUARD:-GUARD].reshape(expect.shape)
+    assert (got[1] == CANARY).all(), "frame 1 (a negative entry) was written"
+    bad = np.argwhere(got[0] != expect[0])
+    assert bad.size == 0, f"frame 0: {len(bad)} wrong bytes, first at (row, byte) {bad[:4].tolist()}"
+
+
 def test_guards_refuse_and_write_nothing(native):
     import torch
 

@@ -185,6 +185,41 @@ def test_raw_kernel_frames_and_dims(native, depth, in_place):
     _unsharp_case(native, rng, depth, 24, top // 8, rb, h, in_place, frames=4, dims=dims)
 
 
+def test_kernel_clamps_a_device_table_that_disagrees_with_its_host_copy(native):
+    """The guards read the host list; the kernel reads the device table and
+    clamps each entry to the envelope.  Entries beyond the envelope give
+    exactly the envelope, entries below zero leave the frame alone.  (Unclamped,
+    the 16 bytes and the one row more would land in frame 0's pad and ghost row,
+    inside the buffer: a wrong kernel fails the comparison.)"""
+    import torch
+
+    rng = np.random.default_rng(977)
+    rb, h, frames, k, t = 40, 5, 2, 24, 31
+    x, b = _samples(rng, 8, (frames, h, rb), k, t)
+    xo, pitch = _frames(x, rb, h, frames, DIRTY)
+    xb, _ = _frames(b, rb, h, frames, DIRTY)
+    assert rb + 16 <= pitch - 16
+    expect = np.full_like(xb, CANARY)
+    expect[0, 1:1 + h, 16:16 + rb] = _formula(x[0], b[0], k, t, 255).astype(np.uint8)
+    orig, blur, dst = _device(xo), _device(xb), _device(np.full_like(xb, CANARY))
+    table = torch.tensor([[rb + 16, h + 1], [-1, -1]], dtype=torch.int32, device="cuda")
+    off, stride = GUARD + pitch + 16, (h + 2) * pitch
+    torch.cuda.synchronize()
+    native.launch_unsharp(orig.data_ptr() + off, pitch, blur.data_ptr() + off, pitch, dst.data_ptr() + off, pitch, rb,
+                          h, depth=8, k=k, threshold=t, frames=frames, orig_stride=stride, blur_stride=stride,
+                          dst_stride=stride, stream=torch.cuda.current_stream().cuda_stream,
+                          dims=[(rb, h), (rb, h)], dims_ptr=table.data_ptr())
+    torch.cuda.synchronize()
+    got = dst.cpu().numpy()
+    assert (got[:GUARD] == CANARY).all() and (got[-GUARD:] == CANARY).all(), "a canary outside the frames"
+    got = got[GUARD:-GUARD].reshape(expect.shape)
+    assert np.array_equal(got[1], expect[1]), "frame 1 (a negative entry) was written"
+    bad = np.argwhere(got[0] != expect[0])
+    assert bad.size == 0, f"frame 0: {len(bad)} wrong bytes, first at (row, byte) {bad[:4].tolist()}"
+    assert np.array_equal(orig.cpu().numpy()[GUARD:-GUARD], xo.reshape(-1))
+    assert np.array_equal(blur.cpu().numpy()[GUARD:-GUARD], xb.reshape(-1))
+
+
 def test_guards_refuse_and_write_nothing(native):
     import torch
 
