@@ -1,6 +1,8 @@
-"""Harness of tests/test_gpu_tile_edges.py: tile geometry of the fused 8-bit
-kernels, sizes derived from it, test images, dirty canary-guarded frames and
-the byte-for-byte comparison of a launch's whole destination allocation.
+"""Harness of tests/test_gpu_tile_edges.py and tests/test_gpu_single_step.py:
+tile geometry of the fused 8-bit kernels and lane / workgroup geometry of the
+single-step ones, sizes derived from them, test images, dirty canary-guarded
+frames and the byte-for-byte comparison of a launch's whole destination
+allocation.
 
 Imports NumPy only; torch is imported inside launch()."""
 import math
@@ -99,7 +101,120 @@ def bufop_sizes(m, nw, c, steps):
     return out
 
 
+# ---- the single-step kernels (k_binomial, k_generic9) ------------------------------
+# A lane owns 16 row bytes, a workgroup is 64 lanes (1024 row bytes) x 4 row
+# groups; a lane of k_binomial marches down RPT = 4 rows, one of k_generic9
+# makes one row.
+
+LANE = 16
+WG_BYTES = 64 * LANE
+RPT = 4
+WG_ROWS = {"binomial": 4 * RPT, "generic9": 4}
+SINGLE_STEP_HEIGHTS = {"binomial": (1, 2, 3, RPT, RPT + 1, 4 * RPT - 1, 4 * RPT, 4 * RPT + 1, 2 * 4 * RPT + 1),
+                       "generic9": (1, 2, 3, 4, 5, 2 * 4 + 1)}
+
+
+def partial_valids(c):
+    """The smallest and the largest count of valid bytes (1..15) a row of whole
+    c-byte pixels can leave in its last lane: 1 and 15 for grey and RGB; an
+    RGBA row ends on a multiple of 4 bytes, so 4 and 12."""
+    g = math.gcd(c, LANE)
+    return g, LANE - g
+
+
+def single_step_widths(c):
+    """Pixel widths of c-byte pixels: one and two pixels; the whole-pixel
+    widths nearest below, at (where c divides it) and above one lane, two
+    lanes, one workgroup and two workgroups (the last: three workgroups in x);
+    the smallest rows that end on each of partial_valids(c) bytes of a lane
+    and on a full lane."""
+    ws = [1, 2]
+    for edge in (LANE, 2 * LANE, WG_BYTES, 2 * WG_BYTES):
+        ws += [(edge - 1) // c] + ([edge // c] if edge % c == 0 else []) + [edge // c + 1]
+    for valid in partial_valids(c) + (0,):  # 0: the row's last lane is full (RGB: 48 bytes)
+        ws += [w for w in range(1, 2 * LANE + 1) if (w * c) % LANE == valid][:1]
+    return sorted({w for w in ws if w >= 1})
+
+
+def seam_widths(c):
+    """The widths of single_step_widths(c) either side of (and at) the 1024-byte seam."""
+    return [w for w in single_step_widths(c) if abs(w * c - WG_BYTES) <= c]
+
+
+def single_step_sizes(kernel, c):
+    """[(h, w)] in pixels for `kernel` ("binomial" | "generic9"), paired and not
+    multiplied out: the seam widths at every height up to one row group and a
+    row; the taller heights at a width just past the seam, at the narrowest
+    partial last lane and at three workgroups; every other width once, the
+    heights taken in turn."""
+    hs = SINGLE_STEP_HEIGHTS[kernel]
+    ws = single_step_widths(c)
+    small = [h for h in hs if h <= 5]
+    tall = [h for h in hs if h > 5]
+    seam = seam_widths(c)
+    few = [max(seam), min(w for w in ws if (w * c) % LANE == partial_valids(c)[0]), max(ws)]
+    out = [(h, w) for w in seam for h in small] + [(h, w) for h in tall for w in few]
+    out += [(hs[i % len(hs)], w) for i, w in enumerate(w for w in ws if w not in seam)]
+    seen, uniq = set(), []
+    for s in out:
+        if s not in seen:
+            seen.add(s)
+            uniq.append(s)
+    return uniq
+
+
 # ---- images (h, rb) uint8 -----------------------------------------------------
+
+
+def half_lane_stripes(h, rb, low):
+    """255 in the low (bytes x % 16 < 8) or the high half of every 16-byte lane,
+    0 in the other: the two 16-bit halves of k_binomial's pairs (b_k, b_k+8)
+    hold the maximum beside zero."""
+    lit = (np.arange(rb) % LANE < LANE // 2) == bool(low)
+    return np.repeat(np.where(lit, 255, 0).astype(np.uint8)[None], h, axis=0)
+
+
+def untouched_zero_columns(img, c):
+    """Byte columns of img that are zero and whose neighbours c bytes to the
+    left and to the right are zero (or outside the row) in every row: a 3 x 3
+    step under the zero border leaves them zero whatever its taps."""
+    z = ~img.any(axis=0)
+    left = np.concatenate([np.ones(c, bool), z[:-c]]) if img.shape[1] > c else np.ones_like(z)
+    right = np.concatenate([z[c:], np.ones(c, bool)]) if img.shape[1] > c else np.ones_like(z)
+    return z & left & right
+
+
+def impulses(h, rb, c, flip=False):
+    """Single 255 pixels on black, at least 3 pixels apart in x or in y, so
+    that every tap of a 3 x 3 filter shows alone: on the pixels that hold the
+    bytes either side of the 1024-byte seam, the row's first and last byte and
+    a lane's last and the next lane's first byte, tried in the first and then
+    in the last row.  Neighbouring targets cannot share a row; `flip` gives the
+    other one of each pair the first pick.  Returns (image, impulse count)."""
+    pairs = [(WG_BYTES - 1, WG_BYTES), (0, rb - 1), (LANE - 1, LANE), (WG_BYTES - LANE, WG_BYTES + LANE - 1)]
+    targets = [b for p in pairs for b in (p[::-1] if flip else p) if 0 <= b < rb]
+    img = np.zeros((h, rb), np.uint8)
+    placed = []
+    for y in dict.fromkeys((0, h - 1)):
+        for b in targets:
+            px = b // c
+            if all(max(abs(y - py), abs(px - qx)) >= 3 for py, qx in placed) and (y, px) not in placed:
+                placed.append((y, px))
+                img[y, px * c:(px + 1) * c] = 255
+    return img, len(placed)
+
+
+def exact_sums(img, c, taps):
+    """sum tap x sample of one 3 x 3 step under the zero border, in int64: what
+    the clamps at 0 and at 255 are applied to, before the division."""
+    h, rb = img.shape
+    p = np.pad(img.astype(np.int64).reshape(h, rb // c, c), ((1, 1), (1, 1), (0, 0)))
+    s = np.zeros((h, rb // c, c), np.int64)
+    for k in range(3):
+        for l in range(3):
+            s += int(taps[3 * k + l]) * p[k:k + h, l:l + rb // c]
+    return s.reshape(h, rb)
+
 
 
 def values8(rng, h, rb):
@@ -139,11 +254,15 @@ def deep_zero_columns(rb, vs, c, steps, lit):
 # ---- frames ---------------------------------------------------------------------
 
 
-def frames(lay, halo, rows_img, top_ghosts=0, bottom_ghosts=0):
+def frames(lay, halo, rows_img, top_ghosts=0, bottom_ghosts=0, pads="dirty"):
     """(clean, dirty) frames ((h + 2 halo, pitch) uint8) of rows_img ((h + 2
     halo, rb): ghost rows included).  Frame rows [0, top_ghosts) and the last
     bottom_ghosts ones lie outside the global image.  clean: zeros there and in
-    every pad; dirty: 0xFF there, in the 16 left pad bytes and right of rb."""
+    every pad; dirty: 0xFF there, in the 16 left pad bytes and right of rb.
+    pads="zero" is the single-step kernels' contract (they take the left and
+    right boundary from the frame's pad): the pads of every row inside the
+    global image stay zero, the rows outside it are 0xFF from end to end."""
+    assert pads in ("dirty", "zero")
     n, rb = rows_img.shape
     clean = np.zeros((n, lay["pitch"]), np.uint8)
     clean[:, PAD:PAD + rb] = rows_img
@@ -152,8 +271,9 @@ def frames(lay, halo, rows_img, top_ghosts=0, bottom_ghosts=0):
     dirty = clean.copy()
     dirty[:top_ghosts] = 0xFF
     dirty[n - bottom_ghosts:] = 0xFF
-    dirty[:, :PAD] = 0xFF
-    dirty[:, PAD + rb:] = 0xFF
+    if pads == "dirty":
+        dirty[:, :PAD] = 0xFF
+        dirty[:, PAD + rb:] = 0xFF
     assert n == 2 * halo + lay["rows"] and dirty.size == lay["bytes"]
     return clean, dirty
 
@@ -184,13 +304,19 @@ def launch(native, dirty, lay, halo, filt, c, r0, r1, steps, g_row0, height, bor
     return dst.cpu().numpy()
 
 
-def expected(shape, lay, halo, ref_rows, lo, hi):
+def expected(shape, lay, halo, ref_rows, lo, hi, tail_zeros=False):
     """The destination allocation a launch must leave: canary everywhere but
-    frame rows [lo, hi) x bytes [0, rb), which hold ref_rows ((hi - lo, rb))."""
+    frame rows [lo, hi) x bytes [0, rb), which hold ref_rows ((hi - lo, rb)).
+    tail_zeros: the vector-store contract of the single-step kernels, whose
+    lanes store whole 16-byte vectors — bytes [rb, round_up(rb, 16)) of those
+    rows hold 0, and everything else is canary all the same."""
     want = np.full(shape[0] * shape[1] + 2 * GUARD, CANARY, np.uint8)
     fr = want[GUARD:-GUARD].reshape(shape)
     if lo < hi:
-        fr[halo + lo:halo + hi, PAD:PAD + lay["row_bytes"]] = ref_rows
+        rb = lay["row_bytes"]
+        fr[halo + lo:halo + hi, PAD:PAD + rb] = ref_rows
+        if tail_zeros:
+            fr[halo + lo:halo + hi, PAD + rb:PAD + -(-rb // LANE) * LANE] = 0
     return want
 
 
